@@ -4,7 +4,15 @@ the 10-link pendulum on a cart at N = 100 000 collocation nodes (BASELINE.json
 metric, ``configs[2]`` on one GPU, ``configs[3]`` on several), inputs resident
 in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline.
+``--full`` adds everything else the benchmark measures or checks: the
+per-kernel times and the roofline, the check of the benched launch against
+the reference's golden record, the serial pair, the other configurations,
+the host path, the CPU baseline and (N > 1) the re-assembly variants.
+``--dump-outputs DIR`` writes what the last timed step computed under DIR
+(:func:`dump_outputs`).
 
 One *step* = one ``constraints(free)`` + one ``jacobian(free)`` on a free
 vector that differs from the previous step's (rotating set of synthetic
@@ -13,7 +21,7 @@ device pointers on torch's current stream.  Both outputs of a step come from
 ONE launch (``opty_hip_eval_con_jac`` / ``opty_hip_eval_shard``: the Jacobian
 waves plus one constraint wave per 64-node block); ``--serial`` issues two
 launches (constraints, then Jacobian -- the order IPOPT calls them in)
-instead, and the default run also reports that figure as
+instead, and ``--full`` also reports that figure as
 ``config.serial_evals_per_s``.
 
 Multi-GPU (``--gpus N`` under ``torch.distributed.run``) is BASELINE config 4:
@@ -21,8 +29,9 @@ the 100 000 nodes of ONE problem are sharded over the ranks, one contiguous
 node range each with a one-node halo (``opty_amd.sharded``) --
 **strong scaling**, ``value`` = evaluations of the whole problem per second
 with every rank's slice of the outputs left in its own HBM (no data-path
-collective).  The same K steps are then re-timed with the two re-assembly
-variants SURVEY.md 8(e) lists, reported in ``config.variants``:
+collective).  With ``--full`` the same K steps are then re-timed with the
+two re-assembly variants SURVEY.md 8(e) lists, reported in
+``config.variants``:
 ``gather`` (+ RCCL point-to-point gather-v of constraints and Jacobian to rank
 0) and ``to_host`` (+ every rank copying its shard over its own PCIe link
 into one page-locked host vector shared by all ranks).  ``--weak`` instead
@@ -207,6 +216,46 @@ def lookup_traffic(kernel_sha):
             return json.load(f)[kernel_sha]['hbm_bytes_per_launch']
     except (OSError, KeyError, ValueError, TypeError):
         return None
+
+
+#: ``--dump-outputs``: bytes all files of a run may take, and constraint nodes
+#: of the fixed, seeded sample of the Jacobian (the whole Jacobian of the
+#: benchmark is 792 MB)
+DUMP_BYTES = 64 << 20
+DUMP_NODES = 4096
+
+
+def dump_outputs(path, con2d, jac2d, a, b, ncn, suffix=''):
+    """``--dump-outputs``: what the last timed step computed, as float64
+    ``.npy`` files under ``path``.  ``con2d`` (M, b-a) / ``jac2d`` (b-a, P)
+    are the outputs of the launch's constraint nodes [a, b) of ``ncn``
+    (device tensors or arrays).  Written: ``jac_sample`` (k, P), the Jacobian
+    blocks of a fixed, seeded sample of the ``ncn`` nodes (the first and the
+    last node included; the part of it in [a, b)), their global node indices
+    ``jac_sample_nodes``, and ``con`` (M, b-a), the constraints whole -- or,
+    where they would take more than half of :data:`DUMP_BYTES`,
+    ``con_sample`` (M, k) at the same nodes.  ``suffix`` tells the ranks of a
+    multi-GPU run apart."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    nodes = np.unique(np.concatenate([
+        rng.choice(ncn, min(DUMP_NODES, ncn), replace=False), [0, ncn - 1]]))
+    nodes = nodes[(nodes >= a) & (nodes < b)]
+    sel = nodes - a
+    whole_con = 8*con2d.shape[0]*ncn <= DUMP_BYTES//2
+    if isinstance(jac2d, np.ndarray):
+        jac = jac2d[sel]
+        con = con2d if whole_con else con2d[:, sel]
+    else:
+        import torch
+        idx = torch.from_numpy(sel).to(jac2d.device)
+        jac = jac2d[idx].cpu().numpy()
+        con = (con2d if whole_con else con2d[:, idx]).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (('con' if whole_con else 'con_sample', con),
+                      ('jac_sample', jac), ('jac_sample_nodes', nodes)):
+        np.save(os.path.join(path, name + suffix + '.npy'),
+                np.ascontiguousarray(arr, dtype=np.float64))
 
 
 #: entries of ``other_configs`` that are also timed with parameter-specialised
@@ -720,16 +769,23 @@ def main_no_torch(args):
     barrier()
     el = time.perf_counter() - t0
     parts = side.gather_bytes(repr(el).encode(), 0)
-    jac_ms = hip.time_eval_shard(hb.EVAL_JAC, frees[0], None, cnt, jac, a, b,
-                                 args.steps)
-    con_ms = hip.time_eval_shard(hb.EVAL_CON, frees[1], con, cnt, None, a, b,
-                                 args.steps)
-    fused_ms = hip.time_eval_shard(hb.EVAL_FUSED, frees[2], con, cnt, jac, a,
-                                   b, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, con.numpy().reshape(M, cnt),
+                     jac.numpy().reshape(cnt, P), a, b, N - 1,
+                     '' if world == 1 else '_rank%d' % rank)
+    if args.full:
+        jac_ms = hip.time_eval_shard(hb.EVAL_JAC, frees[0], None, cnt, jac,
+                                     a, b, args.steps)
+        con_ms = hip.time_eval_shard(hb.EVAL_CON, frees[1], con, cnt, None,
+                                     a, b, args.steps)
+        fused_ms = hip.time_eval_shard(hb.EVAL_FUSED, frees[2], con, cnt,
+                                       jac, a, b, args.steps)
     # what was benched, against the reference's golden record
     verify = {'ok': None, 'skipped': 'no reference golden for N = %d'
               % args.nodes}
-    if args.nodes == 100000 and strong:
+    if not args.full:
+        verify = {'ok': None, 'skipped': 'checked with --full'}
+    elif args.nodes == 100000 and strong:
         step(0)
         hip.synchronize()
         ver = _Verifier(M, P, N, None)
@@ -753,16 +809,15 @@ def main_no_torch(args):
         free_bytes = 8.0*((col.num_states +
                            col.num_unknown_input_trajectories)*(cnt + 1))
         if args.serial or not route['fused_pays']:
-            dom, dom_ms = 'opty_jac', jac_ms
+            dom = 'opty_jac'
             dom_bytes = free_bytes + 8.0*P*cnt
         else:
-            dom, dom_ms = 'opty_conjac', fused_ms
+            dom = 'opty_conjac'
             dom_bytes = free_bytes + 8.0*M*cnt + 8.0*P*cnt
-        achieved = dom_bytes/(dom_ms*1e-3)/1e9
         kmeta = col._kernel_meta['kernels'][
             'jac' if dom == 'opty_jac' and not route['jac_via_fused']
             else 'conjac']
-        print(json.dumps({
+        line = {
             'metric': 'constraint+Jacobian evals/sec at N=100k nodes '
                       '(10-link pendulum on cart, backward Euler)',
             'value': args.steps*(1 if strong else world)/elapsed,
@@ -785,17 +840,22 @@ def main_no_torch(args):
                 'oversubscribed': bool(oversub),
                 'prewarm_ms': args.prewarm_ms, 'build_check': build,
                 'routing': route, 'kernel_sha': kmeta['sha'][:16],
-                'kernel_ms': {'opty_jac': jac_ms, 'opty_con': con_ms,
-                              'opty_conjac': fused_ms},
                 'nodes_per_launch': cnt, 'verify': verify},
-            'roofline': {
+        }
+        if args.full:
+            dom_ms = jac_ms if dom == 'opty_jac' else fused_ms
+            achieved = dom_bytes/(dom_ms*1e-3)/1e9
+            line['config']['kernel_ms'] = {
+                'opty_jac': jac_ms, 'opty_con': con_ms,
+                'opty_conjac': fused_ms}
+            line['roofline'] = {
                 'bound': 'hbm', 'kernel': dom, 'achieved': achieved,
                 'algorithmic_bytes_per_launch': dom_bytes,
                 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                 'frac': achieved/HBM_PEAK_GBS,
                 'traffic': lookup_traffic(kmeta['sha'])
-                if (world == 1 and args.nodes == 100000) else None},
-        }))
+                if (world == 1 and args.nodes == 100000) else None}
+        print(json.dumps(line))
     assert not loaded_torch, 'torch was imported in --no-torch mode'
     for v in frees + [con, jac]:
         v.close()
@@ -824,13 +884,24 @@ def main():
     ap.add_argument('--prewarm-ms', type=float, default=150.0,
                     help='untimed clock-ramp phase before the warm-up steps '
                          '(wall milliseconds of the same step; 0 disables)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, everything else the benchmark '
+                         'measures or checks: per-kernel times and roofline, '
+                         'the check against the reference\'s golden record, '
+                         'the secondary figures and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as .npy '
+                         'files under DIR (constraints whole, a fixed sample '
+                         'of the Jacobian\'s node blocks)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='(internal) time the CPU baseline in this process '
                          'and print its JSON')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the secondary figures (serial pair, host path, '
-                         'other configs, re-assembly variants)')
+                    help='with --full: skip the secondary figures (serial '
+                         'pair, host path, other configs, re-assembly '
+                         'variants)')
     ap.add_argument('--no-torch', action='store_true',
                     help='the same step and line from a process that never '
                          'imports torch: device memory, launches, hipEvent '
@@ -946,53 +1017,15 @@ def main():
             k += 1
         torch.cuda.synchronize()
     elapsed = timed(step, args.steps, args.warmup)
+    if args.dump_outputs:
+        # (before anything else is launched: the buffers hold the last
+        # timed step's outputs)
+        dump_outputs(args.dump_outputs, con, jac.view(b - a, P), a, b, N - 1,
+                     '' if world == 1 else '_rank%d' % rank)
 
-    # Kernel durations, measured live with HIP events on the launch stream.
-    jac_ms = hip.time_eval_shard(hb.EVAL_JAC, frees[0], None, cs, jac, a, b,
-                                 args.steps)
-    con_ms = hip.time_eval_shard(hb.EVAL_CON, frees[1], con, cs, None, a, b,
-                                 args.steps)
-    fused_ms = hip.time_eval_shard(hb.EVAL_FUSED, frees[2], con, cs, jac, a,
-                                   b, args.steps)
-    barrier()
-
-    # ---- verification of what was benched (after the timed region) ----------
-    # frees[0] is the seed-0 vector the reference's golden record of this
-    # workload was made with; the check runs the very launch that was timed.
-    verifier = None
-    verify = {'ok': None, 'skipped': 'no reference golden for N = %d'
-              % args.nodes}
-    if args.nodes == 100000:
-        verifier = _Verifier(M, P, N, dev)
-
-    def reduce_sum(t):
-        if world > 1 and strong:
-            if oversub:
-                h = t.cpu()
-                dist.all_reduce(h)
-                return h
-            dist.all_reduce(t)
-        return t.cpu()
-
-    def check_sums(con2d, jac2d, label, reduce=True):
-        part = torch.cat([jac2d.sum(0), con2d.sum(1),
-                          jac2d.abs().sum().view(1),
-                          con2d.abs().sum().view(1)])
-        part = (reduce_sum(part) if reduce else part.cpu()).numpy()
-        verifier.sums(part[:P], part[P:P + M], part[P + M], part[P + M + 1],
-                      label)
-
-    if verifier is not None:
-        step(0)
-        torch.cuda.synchronize()
-        jac2d = jac.view(b - a, P)
-        if strong or rank == 0:
-            verifier.nodes(con, jac2d, a, b, 'benched launch')
-        if strong or world == 1:
-            check_sums(con, jac2d, 'benched launch')
-
-    def headline(extras, verify):
-        """The JSON line (rank 0)."""
+    def headline(extras, verify, kernel_ms=None):
+        """The JSON line (rank 0); ``kernel_ms``: the per-kernel times of
+        ``--full`` (and with them the roofline), None in a plain run."""
         cnt = b - a
         free_bytes = 8.0*((col.num_states +
                            col.num_unknown_input_trajectories)*(cnt + 1))
@@ -1005,16 +1038,13 @@ def main():
             # (two launches per step -- asked for, or because the handle
             # measured opty_con + opty_jac faster than the fused kernel on
             # this device: the Jacobian kernel is the dominant one)
-            dom, dom_ms, dom_bytes = 'opty_jac', jac_ms, jac_bytes
+            dom, dom_bytes = 'opty_jac', jac_bytes
         else:
-            dom, dom_ms = 'opty_conjac', fused_ms
+            dom = 'opty_conjac'
             dom_bytes = free_bytes + 8.0*M*cnt + 8.0*P*cnt
-        achieved = dom_bytes/(dom_ms*1e-3)/1e9
         kmeta = col._kernel_meta['kernels'][
             'jac' if dom == 'opty_jac' and not route['jac_via_fused']
             else 'conjac']
-        traffic = lookup_traffic(kmeta['sha']) \
-            if (world == 1 and args.nodes == 100000) else None
         value = args.steps*(1 if strong else world)/elapsed
         nnz_total = P*(N - 1)*(1 if strong else world)
         out = {
@@ -1052,22 +1082,81 @@ def main():
                 'kernel_sha': kmeta['sha'][:16],
                 'jac_waves_per_block': hip.desc['jac_wgs_per_block'] *
                 hip.desc['jac_waves_per_wg'],
-                'GBps_nnz_written': 8.0*P*cnt/(jac_ms*1e-3)/1e9,
-                'kernel_ms': {'opty_jac': jac_ms, 'opty_con': con_ms,
-                              'opty_conjac': fused_ms},
                 'nodes_per_launch': cnt,
             },
-            'roofline': {
+        }
+        if kernel_ms is not None:
+            dom_ms = kernel_ms[dom]
+            achieved = dom_bytes/(dom_ms*1e-3)/1e9
+            traffic = lookup_traffic(kmeta['sha']) \
+                if (world == 1 and args.nodes == 100000) else None
+            out['config']['GBps_nnz_written'] = \
+                8.0*P*cnt/(kernel_ms['opty_jac']*1e-3)/1e9
+            out['config']['kernel_ms'] = kernel_ms
+            out['roofline'] = {
                 'bound': 'hbm', 'kernel': dom, 'achieved': achieved,
                 'algorithmic_bytes_per_launch': dom_bytes,
                 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': achieved/HBM_PEAK_GBS, 'traffic': traffic},
-        }
+                'frac': achieved/HBM_PEAK_GBS, 'traffic': traffic}
         out['config'].update(extras)
         out['config']['verify'] = verify
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(args.nodes)
         return out
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline({}, {'ok': None,
+                                           'skipped': 'checked with --full'})))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # Kernel durations, measured live with HIP events on the launch stream.
+    jac_ms = hip.time_eval_shard(hb.EVAL_JAC, frees[0], None, cs, jac, a, b,
+                                 args.steps)
+    con_ms = hip.time_eval_shard(hb.EVAL_CON, frees[1], con, cs, None, a, b,
+                                 args.steps)
+    fused_ms = hip.time_eval_shard(hb.EVAL_FUSED, frees[2], con, cs, jac, a,
+                                   b, args.steps)
+    kernel_ms = {'opty_jac': jac_ms, 'opty_con': con_ms,
+                 'opty_conjac': fused_ms}
+    barrier()
+
+    # ---- verification of what was benched (after the timed region) ----------
+    # frees[0] is the seed-0 vector the reference's golden record of this
+    # workload was made with; the check runs the very launch that was timed.
+    verifier = None
+    verify = {'ok': None, 'skipped': 'no reference golden for N = %d'
+              % args.nodes}
+    if args.nodes == 100000:
+        verifier = _Verifier(M, P, N, dev)
+
+    def reduce_sum(t):
+        if world > 1 and strong:
+            if oversub:
+                h = t.cpu()
+                dist.all_reduce(h)
+                return h
+            dist.all_reduce(t)
+        return t.cpu()
+
+    def check_sums(con2d, jac2d, label, reduce=True):
+        part = torch.cat([jac2d.sum(0), con2d.sum(1),
+                          jac2d.abs().sum().view(1),
+                          con2d.abs().sum().view(1)])
+        part = (reduce_sum(part) if reduce else part.cpu()).numpy()
+        verifier.sums(part[:P], part[P:P + M], part[P + M], part[P + M + 1],
+                      label)
+
+    if verifier is not None:
+        step(0)
+        torch.cuda.synchronize()
+        jac2d = jac.view(b - a, P)
+        if strong or rank == 0:
+            verifier.nodes(con, jac2d, a, b, 'benched launch')
+        if strong or world == 1:
+            check_sums(con, jac2d, 'benched launch')
 
     extras = {}
     if not args.no_extras:
@@ -1103,7 +1192,8 @@ def main():
                     extras['variants_error'] = (
                         'watchdog: the re-assembly variants did not finish '
                         'within %.0f s' % limit)
-                    print(json.dumps(headline(extras, local)), flush=True)
+                    print(json.dumps(headline(extras, local, kernel_ms)),
+                          flush=True)
                 os._exit(0)
             watchdog = threading.Timer(limit + (0.0 if rank == 0 else 10.0),
                                        give_up)
@@ -1279,7 +1369,7 @@ def main():
         watchdog.cancel()
 
     if rank == 0:
-        print(json.dumps(headline(extras, verify)))
+        print(json.dumps(headline(extras, verify, kernel_ms)))
     if world > 1:
         dist.destroy_process_group()
     if verify['ok'] is False:

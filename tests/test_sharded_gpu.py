@@ -325,7 +325,7 @@ def test_bench_strong_scaling_oversubscribed(world):
            '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(REPO, 'bench.py'),
            '--gpus', str(world), '--steps', '5', '--warmup', '2',
-           '--prewarm-ms', '20', '--no-cpu-baseline']
+           '--prewarm-ms', '20', '--no-cpu-baseline', '--full']
     proc = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO,
                           env=env, timeout=1500)
     assert proc.returncode == 0, proc.stderr[-3000:]
@@ -359,7 +359,7 @@ def test_bench_watchdog_prints_the_headline():
            '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(REPO, 'bench.py'),
            '--gpus', '2', '--steps', '5', '--warmup', '2', '--prewarm-ms',
-           '20', '--no-cpu-baseline']
+           '20', '--no-cpu-baseline', '--full']
     proc = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO,
                           env=env, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
@@ -378,7 +378,7 @@ def test_bench_single_gpu_line_verifies_itself():
     reference's golden record, and the exit code is 0."""
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '5',
            '--warmup', '2', '--prewarm-ms', '20', '--no-cpu-baseline',
-           '--no-extras']
+           '--no-extras', '--full']
     proc = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO,
                           timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
@@ -388,6 +388,53 @@ def test_bench_single_gpu_line_verifies_itself():
     assert ver['ok'] is True and ver['worst_rel'] <= 1e-10, ver
     assert any('checksums over all nodes' in c for c in ver['checked'])
     assert any('sampled nodes' in c for c in ver['checked'])
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """``bench.py`` without ``--full``: the headline line alone (nothing
+    measured or checked besides the timed steps), and ``--dump-outputs``
+    writes what the last timed step computed.  With 5 steps the last one
+    evaluates the seed-0 vector of the reference's golden record, so the
+    dump is held to it."""
+    out = tmp_path/'dump'
+    cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '5',
+           '--warmup', '2', '--prewarm-ms', '20', '--dump-outputs', str(out)]
+    proc = subprocess.run(cmd, capture_output=True, text=True, cwd=REPO,
+                          timeout=900)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    res = json.loads([ln for ln in proc.stdout.splitlines()
+                      if ln.startswith('{')][-1])
+    assert res['steps'] == 5 and res['value'] > 0
+    assert res['ms_per_step'] == pytest.approx(1e3/res['value'])
+    assert 'roofline' not in res and 'cpu_baseline' not in res
+    assert 'kernel_ms' not in res['config']
+    assert res['config']['verify']['ok'] is None
+    meta, z = gu.load('config3_10link')
+    N, M, C = meta['N'], meta['M'], meta['C']
+    P = M*C
+    paths = sorted(out.iterdir())
+    assert [p.name for p in paths] == ['con.npy', 'jac_sample.npy',
+                                       'jac_sample_nodes.npy']
+    assert sum(p.stat().st_size for p in paths) <= 64 << 20
+    con, jac, sample = (np.load(p) for p in paths)
+    assert con.dtype == jac.dtype == sample.dtype == np.float64
+    sample = sample.astype(np.int64)
+    assert con.shape == (M, N - 1) and jac.shape == (len(sample), P)
+    nodes = z['nodes']
+    import opty_amd
+    col = opty_amd.ConstraintCollocator(**problems.build('config3_10link'))
+    free = problems.make_free(col.num_free, seed=meta['seed'])
+    cbn, jbn, _, _ = gu.error_bounds(col, free, nodes)
+    gu.assert_close(con[:, nodes], z['con_nodes'], RTOL,
+                    what='bench dump con nodes', bound=cbn)
+    gu.assert_close(con.sum(axis=1), z['con_eq_sums'], 1e-9,
+                    scale=float(np.abs(con).sum())/M,
+                    what='bench dump con sums')
+    both = np.isin(nodes, sample)
+    assert both[0] and both[-1]         # the first and the last node
+    gu.assert_close(jac[np.searchsorted(sample, nodes[both])],
+                    z['jac_nodes'][both], RTOL, what='bench dump jac nodes',
+                    bound=jbn[both])
 
 
 def _problem_worker(rank, world, port, out):

@@ -8,7 +8,8 @@ mkdir -p gpurun_out/prof_$tag
 grep -a "passed\|failed" gpurun_out/${tag}_suite.log | tail -2
 cp gpurun_out/parity_stats.json gpurun_out/${tag}_parity_stats.json
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-(time timeout 700 python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err) 2>&1 | grep real
+out=$(dirname "$(echo */prof_$tag)")     # the output directory made above
+(time timeout 700 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err) 2>&1 | grep real
 root=$PWD
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $root/gpurun_out/prof_$tag -- \
