@@ -553,6 +553,55 @@ int opty_hip_gather_v(opty_hip_comm *c, opty_hip_problem *p,
                       const double *jac_shard, double *con_global,
                       double *jac_global, int32_t root, int32_t what);
 
+/* ---- exact Hessian of the constraint Lagrangian ------------------------------
+ * hess = sum_k lagrange_k * (second derivatives of constraint k) with respect
+ * to `free`, lower triangle (row >= col on the GLOBAL free indices), as
+ * triplets.  lagrange is ordered like `con`: lagrange[j*(N-1) + i], then the o
+ * instance constraints.  A (row, col) pair REPEATS: the matrix is the SUM of
+ * its triplets (IPOPT's and scipy.sparse.coo_matrix's convention) -- a time
+ * node's diagonal block gets a term from both constraint nodes that share it,
+ * a parameter / h entry one from every node.
+ *   hess : hess[i*PH + e] for constraint node i and per-node entry e, then the
+ *          nnz_inst entries of the instance constraints.
+ * The code object exports `opty_hess` (lane = constraint node; grid.y = the
+ * `strips` pieces of a node's PH entries) and, when nnz_inst > 0,
+ * `opty_hess_inst`.
+ *
+ * A Hessian handle BORROWS its problem handle: device, stream, known
+ * parameters, known trajectories, the fixed node time interval and the
+ * instance atom indices are the problem's own (one copy; what a set_known
+ * call installs is seen by the next Hessian call).  It must be destroyed
+ * before the problem handle. */
+typedef struct opty_hip_hessian opty_hip_hessian;
+
+typedef struct opty_hip_hessian_desc {
+    int32_t PH;        /* stored entries per constraint node                   */
+    int32_t nnz_inst;  /* entries of the instance constraints                  */
+    int32_t strips;    /* workgroups per 64-node block of opty_hess            */
+    /* closed-form index pattern, 4 int32 per per-node entry e:
+     * (row_a, off_a, row_b, off_b); global index of a side = row*N + i + off
+     * for row >= 0, (n+q)*N + off for row == -1 (parameter / h tail) */
+    const int32_t *pattern;
+    const int64_t *inst_rows;   /* nnz_inst global indices each (host memory) */
+    const int64_t *inst_cols;
+} opty_hip_hessian_desc;
+
+int opty_hip_hessian_create(opty_hip_problem *p,
+                            const opty_hip_hessian_desc *desc,
+                            const char *code_object_path,
+                            opty_hip_hessian **out);
+int opty_hip_hessian_destroy(opty_hip_hessian *h);
+/* (N-1)*PH + nnz_inst */
+int64_t opty_hip_hessian_nnz(const opty_hip_hessian *h);
+/* free: num_free doubles, lagrange: num_constraints doubles, hess:
+ * hessian_nnz doubles, all in `mem` memory.  Synchronous for OPTY_HIP_HOST,
+ * enqueued on the problem's stream for OPTY_HIP_DEVICE. */
+int opty_hip_eval_hess(opty_hip_hessian *h, const double *free,
+                       const double *lagrange, double *hess, int32_t mem);
+/* int64 row / column indices of every hess value, same order. */
+int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
+                             int64_t *cols, int32_t mem);
+
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);
 

@@ -40,8 +40,11 @@ UNARY = ('sqrt', 'sin', 'cos', 'tan', 'exp', 'log', 'abs', 'sign', 'asin',
 #: trajectory row (state or input trajectory) at the "current" and "adjacent"
 #: time node (``opty/direct_collocation.py:2350-2364``); ``par`` is a
 #: node-invariant parameter, ``h`` the node time interval, ``free`` one entry
-#: of the free vector at a fixed index (instance constraints).
-INPUT_KINDS = ('cur', 'adj', 'par', 'h', 'free')
+#: of the free vector at a fixed index (instance constraints).  ``lam`` is the
+#: Lagrange multiplier of equation ``index`` at the constraint node,
+#: ``lagrange[index*(N-1) + i]`` (Hessian programs,
+#: ``program.build_hessian_program``): per node, so NOT node-invariant.
+INPUT_KINDS = ('cur', 'adj', 'par', 'h', 'free', 'lam')
 
 
 class DAG(object):

@@ -183,6 +183,189 @@ def build_program(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
         pruned=bool(prune_zeros), layout=layout, row_start=row_start)
 
 
+def column_side(n, q, method, k):
+    """Where wrt column ``k`` of the block lives in ``free`` at constraint
+    node i (the closed form of ``_column_key``): ``(row, off)`` -- free index
+    ``row*N + i + off`` -- or ``(-1, j)`` -- the tail entry ``(n+q)*N + j``
+    (unknown parameter / free interval)."""
+    be = method == 'backward euler'
+    cur, adj = (1, 0) if be else (0, 1)
+    if k < n:
+        return k, cur
+    if k < 2*n:
+        return k - n, adj
+    j = k - 2*n
+    if j < q:
+        return n + j, cur
+    if not be and j < 2*q:
+        return n + j - q, adj
+    return -1, j - (q if be else 2*q)
+
+
+def _side_order(side):
+    """Sort key equal to the order of the free index of a side at every
+    node (N >= 2): trajectory rows first, by row then offset; the tail
+    last."""
+    row, off = side
+    return (1, off, 0) if row < 0 else (0, row, off)
+
+
+class HessianProgram(CollocationProgram):
+    """Plain data of a Hessian program (:func:`build_hessian_program`).
+
+    ``hess_out``: PH node ids, one per stored entry of a constraint node;
+    ``hess_pairs[e] = (a, b)``: the wrt columns of entry ``e`` with ``a`` the
+    row -- the larger GLOBAL free index -- and ``b`` the column;
+    ``inst_hess_out``: node ids of the instance constraints' second partials
+    (NOT multiplied by their multipliers), ``inst_hess_con[t]`` the
+    instance constraint of entry ``t``, ``inst_hess_atoms[t] = (a, b)`` its
+    atoms (indices into the atom list, free index of ``a`` >= that of
+    ``b``)."""
+
+    @property
+    def PH(self):
+        return len(self.hess_out)
+
+    def index_pattern(self):
+        """``[(row_a, off_a, row_b, off_b)]`` per stored entry
+        (:func:`column_side` of both columns)."""
+        return [column_side(self.n, self.q, self.method, a) +
+                column_side(self.n, self.q, self.method, b)
+                for a, b in self.hess_pairs]
+
+
+def hessian_indices(prog, N, atom_free_index):
+    """Closed-form ``(rows, cols)`` (int64) of every value of a Hessian
+    program for ``N`` collocation nodes: node-major blocks
+    ``[i*PH + e]``, then the instance entries; ``atom_free_index[a]`` = free
+    index of instance atom ``a``."""
+    import numpy as np
+    pat = np.array(prog.index_pattern(), dtype=np.int64).reshape(-1, 4)
+    i = np.arange(N - 1, dtype=np.int64)[:, None]
+    tail = (prog.n + prog.q)*N
+
+    def side(row, off):
+        return np.where(row >= 0, row*N + i + off, tail + off)
+    rows = side(pat[:, 0], pat[:, 1]).ravel()
+    cols = side(pat[:, 2], pat[:, 3]).ravel()
+    idx = np.asarray(atom_free_index, dtype=np.int64)
+    irows = np.array([idx[a] for a, _ in prog.inst_hess_atoms],
+                     dtype=np.int64)
+    icols = np.array([idx[b] for _, b in prog.inst_hess_atoms],
+                     dtype=np.int64)
+    return np.concatenate((rows, irows)), np.concatenate((cols, icols))
+
+
+def build_hessian_program(discrete_eom, state_cur, state_adj, traj_cur,
+                          traj_adj, num_known_traj, parameters, num_known_par,
+                          h_sym, variable_duration, wrt, method,
+                          instance=None, implicit=()):
+    """The exact Hessian of the constraint Lagrangian: arguments as
+    :func:`build_program`'s (same lowering, same ``wrt`` columns, same
+    implicit inputs).  At every constraint node it forms
+    ``L_i = sum_j lam_j c_j`` over INPUT nodes ``('lam', j)``, differentiates
+    it twice with :func:`lower.forward_jacobian` over the block's C columns
+    and keeps the structurally nonzero entries of the LOWER triangle --
+    lower on the global free indices: the same orientation at every node
+    (:func:`column_side`), so the per-node pattern is closed form.  Instance
+    constraint ``k`` contributes the second partials of its expression with
+    respect to its atoms (the caller multiplies them by ``lagrange[M*(N-1) +
+    k]``); ``instance`` is ``(expressions, atom symbols, atoms per
+    expression, free index per atom)``.
+
+    Implicit known trajectories are refused: only ``dr/dx`` is known, the
+    second derivative is not."""
+    if implicit:
+        raise NotImplementedError(
+            'the Hessian of a problem with implicit known trajectories (a '
+            'known r(x(t)) with only dr/dx given) is not available: the '
+            'second derivative of r is unknown.')
+    dag = ir.DAG()
+    n = len(state_cur)
+    m = len(traj_cur)
+    q = m - num_known_traj
+    r = len(parameters) - num_known_par
+    table = {}
+    for k, s in enumerate(state_cur):
+        table[s] = dag.input('cur', k)
+    for k, s in enumerate(state_adj):
+        table[s] = dag.input('adj', k)
+    for k, s in enumerate(traj_cur):
+        table[s] = dag.input('cur', n + k)
+    if method == 'midpoint':
+        for k, s in enumerate(traj_adj):
+            table[s] = dag.input('adj', n + k)
+    for k, s in enumerate(parameters):
+        table[s] = dag.input('par', k)
+    table[h_sym] = dag.input('h', 0)
+
+    low = Lowerer(dag, table)
+    con_out = [low.lower(e) for e in discrete_eom]
+    lag = dag.sum([dag.mul(dag.input('lam', j), c)
+                   for j, c in enumerate(con_out)])
+    wrt_nodes = [table[s] for s in wrt]
+    C = len(wrt)
+    grad = forward_jacobian(dag, [lag], wrt_nodes)[0]
+    hess = forward_jacobian(dag, grad, wrt_nodes)
+    order = {k: _side_order(column_side(n, q, method, k)) for k in range(C)}
+    pairs = sorted(((a, b) for a in range(C) for b in range(C)
+                    if order[a] >= order[b] and hess[a][b] != dag.zero),
+                   key=lambda ab: (order[ab[0]], order[ab[1]]))
+    out = [hess[a][b] for a, b in pairs]
+    if out and os.environ.get('OPTY_COLLECT', '1') != '0':
+        out = collect_coefficients(dag, out)
+    kept = [k for k, node in enumerate(out) if node != dag.zero]
+    pairs = [pairs[k] for k in kept]
+    out = [out[k] for k in kept]
+
+    rows = [('free', k) for k in range(n)]
+    rows += [('known', j) for j in range(num_known_traj)]
+    rows += [('free', n + j) for j in range(q)]
+    pars = [('known', k) for k in range(num_known_par)]
+    pars += [('tail', j) for j in range(r)]
+    h = ('tail', r) if variable_duration else ('fixed',)
+
+    inst_out, inst_con, inst_atoms, num_atoms = [], [], [], 0
+    if instance is not None:
+        exprs, atom_syms, grads, free_index = instance
+        itable = {s: dag.input('free', a) for a, s in enumerate(atom_syms)}
+        for k, s in enumerate(parameters[:num_known_par]):
+            itable[s] = dag.input('par', k)
+        ilow = Lowerer(dag, itable)
+        num_atoms = len(atom_syms)
+        pos = {s: a for a, s in enumerate(atom_syms)}
+        for k, (e, atoms) in enumerate(zip(exprs, grads)):
+            if not atoms:
+                continue
+            node = ilow.lower(e)
+            nodes = [itable[s] for s in atoms]
+            g = forward_jacobian(dag, [node], nodes)[0]
+            H = forward_jacobian(dag, g, nodes)
+            fi = [free_index[pos[s]] for s in atoms]
+            # every ORDERED pair on or below the diagonal of the free
+            # indices: two distinct atoms at the same free index (theta(0)
+            # and theta(0.001) both closest to node 0) put both of their
+            # mixed partials on that diagonal entry
+            for a in range(len(atoms)):
+                for b in range(len(atoms)):
+                    if (fi[a] > fi[b] or fi[a] == fi[b] and
+                            (a >= b or atoms[a] != atoms[b])) and \
+                            H[a][b] != dag.zero:
+                        inst_out.append(H[a][b])
+                        inst_con.append(k)
+                        inst_atoms.append((pos[atoms[a]], pos[atoms[b]]))
+
+    return HessianProgram(
+        dag=dag, hess_out=out, hess_pairs=pairs, con_out=con_out, jac_out=[],
+        n=n, m=m, q=q, r=r, s=int(variable_duration), M=len(con_out), C=C,
+        num_known_traj=num_known_traj, num_known_par=num_known_par,
+        rows=rows, pars=pars, h=h, method=method,
+        cur_offset=1 if method == 'backward euler' else 0,
+        adj_offset=0 if method == 'backward euler' else 1,
+        inst_hess_out=inst_out, inst_hess_con=inst_con,
+        inst_hess_atoms=inst_atoms, num_inst_atoms=num_atoms)
+
+
 def matrix_program(dag, outputs, num_vec, num_const, shape):
     """Program of a plain matrix of expressions (the reference's
     ``ufuncify_matrix`` call shape, ``opty/utils.py:639-640``): ``outputs`` are

@@ -1,0 +1,262 @@
+// hessian.cpp -- the Hessian handle of libopty_hip.so: the exact Hessian of
+// the constraint Lagrangian, sum_k lagrange_k d2 con_k / d free^2, lower
+// triangle, as triplets (include/opty_hip.h, "exact Hessian").
+//
+// The handle borrows its problem handle (device, stream, known parameters,
+// known trajectories, h, instance atom indices): one copy of the known data,
+// and what opty_hip_set_known_* installs is what the next call reads.  The
+// generated code object exports `opty_hess` (lane = constraint node, grid.y =
+// strips of the per-node entries) and `opty_hess_inst` (one lane, the
+// instance constraints' entries after the node blocks).
+#include "opty_internal.h"
+
+using namespace opty;
+
+namespace {
+
+// The packed kernarg buffer of opty_hess / opty_hess_inst; must match
+// HESS_PARAMS in opty_amd/codegen/emit_hessian.py.
+struct HessArgs {
+    const double *free_;
+    const double *known_traj;
+    const double *params;
+    const double *lam;
+    const long long *inst_idx;
+    double *hess;
+    double h;
+    long long N;
+};
+
+// Closed-form indices: entry e of constraint node i has the global indices
+// side(pattern[4e], pattern[4e+1]) and side(pattern[4e+2], pattern[4e+3]),
+// side(row, off) = row*N + i + off, or tail + off for row == -1.  The
+// instance entries follow the node blocks (a table; the last block).  One
+// block per node row: consecutive lanes write consecutive int64s.
+__global__ void __launch_bounds__(256)
+opty_hess_indices_kernel(const int *pattern, int PH, long long N,
+                         long long ncn, long long tail, const long long *irows,
+                         const long long *icols, int nnz_inst,
+                         long long *rows, long long *cols) {
+    const long long i = blockIdx.x;
+    if (i < ncn) {
+        for (int e = threadIdx.x; e < PH; e += blockDim.x) {
+            const int ra = pattern[4*e], oa = pattern[4*e + 1];
+            const int rb = pattern[4*e + 2], ob = pattern[4*e + 3];
+            rows[i*PH + e] = ra >= 0 ? (long long)ra*N + i + oa : tail + oa;
+            cols[i*PH + e] = rb >= 0 ? (long long)rb*N + i + ob : tail + ob;
+        }
+    } else {
+        for (int t = threadIdx.x; t < nnz_inst; t += blockDim.x) {
+            rows[ncn*PH + t] = irows[t];
+            cols[ncn*PH + t] = icols[t];
+        }
+    }
+}
+
+}  // namespace
+
+struct opty_hip_hessian {
+    opty_hip_problem *p = nullptr;
+    opty_hip_hessian_desc d{};
+    int device = 0;
+    hipModule_t module = nullptr;
+    hipFunction_t k_hess = nullptr, k_inst = nullptr;
+    int *d_pattern = nullptr;
+    long long *d_irows = nullptr, *d_icols = nullptr;
+    // staging for host callers
+    double *d_free = nullptr, *d_lam = nullptr, *d_hess = nullptr;
+    long long *d_rows = nullptr, *d_cols = nullptr;
+    hipStream_t stream = nullptr;
+    hipStream_t last_stream = nullptr;   // stream of the last enqueued work
+    int64_t ncn() const { return p->d.N - 1; }
+    int64_t nnz() const { return (int64_t)d.PH*ncn() + d.nnz_inst; }
+};
+
+extern "C" {
+
+int opty_hip_hessian_create(opty_hip_problem *p,
+                            const opty_hip_hessian_desc *desc,
+                            const char *code_object_path,
+                            opty_hip_hessian **out) {
+    if (!p || !desc || !code_object_path || !out)
+        return fail("null argument");
+    if (desc->PH < 0 || desc->nnz_inst < 0 || desc->strips < 1)
+        return fail("bad Hessian descriptor (PH %d, nnz_inst %d, strips %d)",
+                    desc->PH, desc->nnz_inst, desc->strips);
+    if (desc->PH > 0 && !desc->pattern) return fail("null index pattern");
+    if (desc->nnz_inst > 0 && (!desc->inst_rows || !desc->inst_cols))
+        return fail("null instance indices");
+    if (desc->nnz_inst > 0 && p->d.num_inst == 0)
+        return fail("instance entries but the problem has no instance "
+                    "constraints");
+    if (int rc = use_device(p)) return rc;
+    auto *h = new opty_hip_hessian;
+    h->p = p;
+    h->d = *desc;
+    h->d.pattern = nullptr;
+    h->d.inst_rows = h->d.inst_cols = nullptr;
+    h->device = p->d.device;
+    hipError_t e = hipModuleLoad(&h->module, code_object_path);
+    if (e != hipSuccess) {
+        delete h;
+        (void)hipGetLastError();
+        return fail("hipModuleLoad(%s) failed: %s", code_object_path,
+                    hipGetErrorString(e));
+    }
+    if ((desc->PH > 0 &&
+         hipModuleGetFunction(&h->k_hess, h->module, "opty_hess") !=
+             hipSuccess) ||
+        (desc->nnz_inst > 0 &&
+         hipModuleGetFunction(&h->k_inst, h->module, "opty_hess_inst") !=
+             hipSuccess)) {
+        (void)hipModuleUnload(h->module);
+        delete h;
+        return fail("opty_hess/opty_hess_inst missing from %s",
+                    code_object_path);
+    }
+    auto upload = [&]() -> int {
+        if (desc->PH > 0) {
+            HIP_TRY(hipMalloc((void **)&h->d_pattern,
+                              (size_t)4*desc->PH*sizeof(int)));
+            HIP_TRY(hipMemcpy(h->d_pattern, desc->pattern,
+                              (size_t)4*desc->PH*sizeof(int),
+                              hipMemcpyHostToDevice));
+        }
+        if (desc->nnz_inst > 0) {
+            const size_t b = (size_t)desc->nnz_inst*sizeof(long long);
+            HIP_TRY(hipMalloc((void **)&h->d_irows, b));
+            HIP_TRY(hipMalloc((void **)&h->d_icols, b));
+            HIP_TRY(hipMemcpy(h->d_irows, desc->inst_rows, b,
+                              hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(h->d_icols, desc->inst_cols, b,
+                              hipMemcpyHostToDevice));
+        }
+        return 0;
+    };
+    if (int rc = upload()) {
+        (void)opty_hip_hessian_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int opty_hip_hessian_destroy(opty_hip_hessian *h) {
+    // (touches nothing of the problem handle, which may be gone already)
+    if (!h) return 0;
+    (void)hipSetDevice(h->device);
+    if (h->last_stream)
+        (void)hipStreamSynchronize(sync_target(h->last_stream));
+    void *bufs[] = {h->d_pattern, h->d_irows, h->d_icols, h->d_free,
+                    h->d_lam, h->d_hess, h->d_rows, h->d_cols};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    if (h->module) (void)hipModuleUnload(h->module);
+    delete h;
+    return 0;
+}
+
+int64_t opty_hip_hessian_nnz(const opty_hip_hessian *h) {
+    return h ? h->nnz() : -1;
+}
+
+int opty_hip_eval_hess(opty_hip_hessian *h, const double *free_,
+                       const double *lagrange, double *hess, int32_t mem) {
+    if (!h || !free_ || !lagrange || !hess) return fail("null argument");
+    if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
+        return fail("bad memory kind %d", mem);
+    opty_hip_problem *p = h->p;
+    if (int rc = use_device(p)) return rc;
+    if (int rc = check_ready(p)) return rc;
+    // the problem's stream, whichever it is now; the staging buffers may
+    // still be in use on the one of the previous call
+    h->stream = p->stream;
+    if (int rc = order_streams(h)) return rc;
+    const long long ncn = h->ncn();
+    const size_t nfree = (size_t)p->num_free(), ncon = (size_t)p->num_con(),
+                 nnz = (size_t)h->nnz();
+    const double *dfree = free_, *dlam = lagrange;
+    double *dhess = hess;
+    if (mem == OPTY_HIP_HOST) {
+        if (int rc = ensure(&h->d_free, nfree)) return rc;
+        if (int rc = ensure(&h->d_lam, std::max<size_t>(1, ncon))) return rc;
+        if (int rc = ensure(&h->d_hess, std::max<size_t>(1, nnz))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_free, free_, nfree*sizeof(double),
+                               hipMemcpyHostToDevice, h->stream));
+        if (ncon)
+            HIP_TRY(hipMemcpyAsync(h->d_lam, lagrange, ncon*sizeof(double),
+                                   hipMemcpyHostToDevice, h->stream));
+        dfree = h->d_free;
+        dlam = h->d_lam;
+        dhess = h->d_hess;
+    }
+    HessArgs a{};
+    a.free_ = dfree;
+    a.known_traj = p->d_known;
+    a.params = p->d_params;
+    a.lam = dlam;
+    a.inst_idx = p->d_inst_idx;
+    a.hess = dhess;
+    a.h = p->h;
+    a.N = p->d.N;
+    size_t size = sizeof a;
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
+                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                      HIP_LAUNCH_PARAM_END};
+    const long long nblk = (ncn + 63)/64;
+    if (h->d.PH > 0 && nblk > 0)
+        HIP_TRY(hipModuleLaunchKernel(h->k_hess, (unsigned)nblk,
+                                      (unsigned)h->d.strips, 1, 64, 1, 1, 0,
+                                      h->stream, nullptr, config));
+    if (h->d.nnz_inst > 0)
+        HIP_TRY(hipModuleLaunchKernel(h->k_inst, 1, 1, 1, 64, 1, 1, 0,
+                                      h->stream, nullptr, config));
+    if (mem == OPTY_HIP_HOST) {
+        if (nnz)
+            HIP_TRY(hipMemcpyAsync(hess, h->d_hess, nnz*sizeof(double),
+                                   hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(sync_target(h->stream)));
+    }
+    return 0;
+}
+
+int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
+                             int64_t *cols, int32_t mem) {
+    if (!h || !rows || !cols) return fail("null argument");
+    if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
+        return fail("bad memory kind %d", mem);
+    opty_hip_problem *p = h->p;
+    if (int rc = use_device(p)) return rc;
+    h->stream = p->stream;
+    if (int rc = order_streams(h)) return rc;
+    const long long ncn = h->ncn();
+    const size_t nnz = (size_t)h->nnz();
+    long long *dr = (long long *)rows, *dc = (long long *)cols;
+    if (mem == OPTY_HIP_HOST) {
+        if (int rc = ensure(&h->d_rows, std::max<size_t>(1, nnz))) return rc;
+        if (int rc = ensure(&h->d_cols, std::max<size_t>(1, nnz))) return rc;
+        dr = h->d_rows;
+        dc = h->d_cols;
+    }
+    const long long tail = (long long)(p->d.n + p->d.q)*p->d.N;
+    const long long blocks = ncn + (h->d.nnz_inst > 0 ? 1 : 0);
+    if (blocks > 0 && nnz > 0) {
+        hipLaunchKernelGGL(opty_hess_indices_kernel, dim3((unsigned)blocks),
+                           dim3(256), 0, h->stream, h->d_pattern, h->d.PH,
+                           (long long)p->d.N, ncn, tail, h->d_irows,
+                           h->d_icols, h->d.nnz_inst, dr, dc);
+        HIP_TRY(hipGetLastError());
+    }
+    if (mem == OPTY_HIP_HOST) {
+        if (nnz) {
+            HIP_TRY(hipMemcpyAsync(rows, h->d_rows, nnz*sizeof(long long),
+                                   hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(cols, h->d_cols, nnz*sizeof(long long),
+                                   hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(sync_target(h->stream)));
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -25,7 +25,8 @@ import sympy as sm
 import sympy.physics.mechanics as me
 
 from .utils import parse_free, sort_sympy
-from .codegen.program import build_program, varying_copies
+from .codegen.program import build_program, build_hessian_program, \
+    varying_copies
 from .codegen.emit_hip import emit_module, EmitOptions
 from . import hip_backend as hb
 
@@ -591,6 +592,273 @@ class ConstraintCollocator(object):
             implicit=self._implicit_chain(), prune_zeros=self._prune_zeros,
             layout='csr' if self._jacobian_layout == 'csr' else 'coo')
         return self._program
+
+    def _build_hessian_program(self):
+        """The Hessian program of the constraint Lagrangian
+        (:func:`opty_amd.codegen.program.build_hessian_program`), built on
+        first use.  Problems whose second derivatives are not available are
+        refused: implicit known trajectories (only ``dr/dx`` is given) and
+        known trajectories given as functions of ``free``."""
+        if getattr(self, '_hessian_program', None) is not None:
+            return self._hessian_program
+        if any(callable(v) for v in self.known_trajectory_map.values()):
+            raise NotImplementedError(
+                'the Hessian of a problem with known trajectories given as '
+                'functions of the free vector is not available.')
+        be = self.integration_method == 'backward euler'
+        instance = None
+        if self.instance_constraints is not None:
+            place = {f: sm.Symbol('opty_atom_%d' % a, real=True)
+                     for a, f in enumerate(self._inst_atoms)}
+            exprs = [sm.sympify(c).xreplace(place)
+                     for c in self.instance_constraints]
+            grads = [[place[f] for f in atoms]
+                     for atoms in self._inst_atoms_per_constraint]
+            idx = self.instance_constraints_free_index_map
+            instance = (exprs, [place[f] for f in self._inst_atoms], grads,
+                        [idx[f] for f in self._inst_atoms])
+        logger.info('Lowering and differentiating the constraint '
+                    'Lagrangian twice.')
+        self._hessian_program = build_hessian_program(
+            list(self.discrete_eom),
+            self.current_discrete_state_symbols,
+            self.previous_discrete_state_symbols if be
+            else self.next_discrete_state_symbols,
+            self.current_discrete_specified_symbols,
+            self.next_discrete_specified_symbols,
+            self.num_known_input_trajectories,
+            self.parameters, self.num_known_parameters,
+            self.time_interval_symbol, self._variable_duration,
+            self._wrt(), self.integration_method, instance,
+            implicit=self._implicit_chain())
+        return self._hessian_program
+
+    #: operations per strip of ``opty_hess`` in the first build; halved (and
+    #: chunks made to recompute what they share) while a build spills
+    _HESS_STRIP_OPS = 1500
+
+    def _build_hessian_code_object(self):
+        """``(hsaco, strips, verdict)`` of the Hessian module: the first
+        build whose kernels spill no vector register (smaller strips, then
+        chunks that recompute what they share), through the static ISA check
+        (a hit: the uniform-sincos sibling is built in its place when it is
+        clean).  A module that spills whatever the cut is refused."""
+        from .codegen.emit_hessian import emit_hessian_module
+        from . import isa_check
+        prog = self._build_hessian_program()
+        names = ('opty_hess', 'opty_hess_inst')
+        budget, forget = self._HESS_STRIP_OPS, False
+        tried = []
+        for _ in range(6):
+            source, cut = emit_hessian_module(prog, budget, forget)
+            hsaco = self._compile(source)
+            spills = hb.vgpr_spills(hsaco, names)
+            tried.append((budget, forget, spills))
+            if not spills:
+                break
+            if budget > 200:
+                budget //= 2
+            else:
+                forget = True
+        else:
+            raise hb.HipBackendError(
+                'every build of the Hessian kernels spills vector registers: '
+                '%s' % tried)
+        hits = isa_check.exec_copies(hsaco, names)
+        if hits:
+            src2, cut2 = emit_hessian_module(prog, budget, forget, fast_trig=2)
+            twin = self._compile(src2)
+            if not hb.vgpr_spills(twin, names) and \
+                    not isa_check.exec_copies(twin, names):
+                hsaco, cut, hits = twin, cut2, {}
+        return hsaco, cut, dict(strips=len(cut), strip_ops=budget,
+                                forget=forget, isa_exec_copies=hits)
+
+    #: constraint nodes the referee compares: the first wave and the last node
+    _HESS_VERIFY_NODES = 64
+
+    def _verify_hessian(self, handle):
+        """Holds a Hessian build to its expression DAG before first use: the
+        kernels, on random ``free`` and ``lagrange`` in device buffers that
+        start as NaN, against the DAG as an instruction tape on the GPU
+        (``opty_hip_tape_run``) on a node window, to 64 units of each entry's
+        own rounding-error bound.  Raises :class:`hip_backend.BuildRejected`."""
+        from .codegen.tape import Tape
+        from .codegen.errbound import evaluate_with_error_bound
+        prog = self._build_hessian_program()
+        N = self.num_collocation_nodes
+        ncn = N - 1
+        rng = np.random.default_rng(17)
+        free = rng.uniform(-1.0, 1.0, self.num_free)
+        if self._variable_duration:
+            free[-1] = 0.01
+        lam = rng.uniform(-1.0, 1.0, self.num_constraints)
+        d_free, d_lam = hb.DeviceVector(free, self._device), \
+            hb.DeviceVector(lam, self._device)
+        d_out = hb.DeviceVector(np.full(handle.nnz, np.nan), self._device)
+        try:
+            handle.evaluate(d_free, d_lam, d_out, hb.DEVICE)
+            self._hip.synchronize()
+            got = d_out.numpy()
+        finally:
+            for v in (d_free, d_lam, d_out):
+                v.close()
+        nodes = np.unique(np.r_[np.arange(min(ncn, self._HESS_VERIFY_NODES)),
+                                ncn - 1])
+        inputs = self._hessian_inputs(free, lam, nodes)
+        roots = list(prog.hess_out) + list(prog.inst_hess_out)
+        tape = Tape(prog.dag, roots)
+        vals = hb.tape_run(tape, tape.table(len(nodes), inputs), self._device)
+        _, bound = evaluate_with_error_bound(prog.dag, roots, inputs)
+        PH = prog.PH
+        u = 2.0**-53
+        worst = 0.0
+        for e, node in enumerate(roots):
+            want = vals[tape.slot[node]]
+            b = np.broadcast_to(np.abs(np.asarray(bound[e], dtype=float)),
+                                want.shape)
+            if e < PH:
+                have = got[nodes*PH + e]
+            else:
+                t = e - PH
+                scale = lam[prog.M*ncn + prog.inst_hess_con[t]]
+                have = np.full(want.shape, got[ncn*PH + t])
+                want, b = want*scale, b*abs(scale)
+            err = np.abs(have - want)
+            tol = 64.0*u*b + 4.0*u*np.abs(want)
+            if not np.all(err <= tol):
+                raise hb.BuildRejected(
+                    'Hessian entry %d disagrees with the instruction tape '
+                    '(max error %.3g)' % (e, np.nanmax(err)),
+                    dict(entry=e, err=float(np.nanmax(err))))
+            worst = max(worst, float(np.max(err/np.maximum(tol, 1e-300))))
+        return dict(ok=True, referee='tape', nodes=len(nodes),
+                    worst_fraction_of_tolerance=worst)
+
+    def _hessian_inputs(self, free, lagrange, nodes):
+        """``inputs(kind, index)`` of the Hessian DAG at the constraint nodes
+        ``nodes`` (an index array) for ``free`` and ``lagrange``."""
+        prog = self._build_hessian_program()
+        N = self.num_collocation_nodes
+        ncn = N - 1
+        n, q = prog.n, prog.q
+        tail = free[(n + q)*N:]
+        known = self._known_trajectory_array(free) \
+            if self.num_known_input_trajectories else None
+        kpar = [float(self.known_parameter_map[p])
+                for p in self.known_parameters]
+        idx = self.instance_constraints_free_index_map \
+            if self.num_instance_constraints else {}
+
+        def inputs(kind, k):
+            if kind in ('cur', 'adj'):
+                src, r = prog.rows[k]
+                row = free[r*N:(r + 1)*N] if src == 'free' else known[r]
+                off = prog.cur_offset if kind == 'cur' else prog.adj_offset
+                return row[nodes + off]
+            if kind == 'lam':
+                return lagrange[k*ncn + nodes]
+            if kind == 'par':
+                src, r = prog.pars[k]
+                return kpar[r] if src == 'known' else tail[r]
+            if kind == 'h':
+                return self.node_time_interval if prog.h[0] == 'fixed' \
+                    else tail[prog.h[1]]
+            assert kind == 'free', kind
+            return free[idx[self._inst_atoms[k]]]
+        return inputs
+
+    def _ensure_hessian(self):
+        """The Hessian handle (built, checked and verified on first use; it
+        borrows the problem handle's device data)."""
+        if getattr(self, '_hessian', None) is not None:
+            return self._hessian
+        hip = self._ensure_hip()
+        prog = self._build_hessian_program()
+        hsaco, cut, meta = self._build_hessian_code_object()
+        rows, cols = self.hessian_indices_closed_form()
+        PH, ncn = prog.PH, self.num_collocation_nodes - 1
+        handle = hb.HipHessian(hip, dict(
+            PH=PH, nnz_inst=len(prog.inst_hess_out), strips=max(1, len(cut)),
+            pattern=np.array(prog.index_pattern(), dtype=np.int32),
+            inst_rows=rows[ncn*PH:], inst_cols=cols[ncn*PH:]), hsaco)
+        self._sync_known(hip, None)
+        try:
+            verdict = self._verify_hessian(handle)
+        except hb.BuildRejected:
+            handle.release()
+            raise
+        self._hessian_meta = dict(meta, hsaco=hsaco, verdict=verdict)
+        self._hessian = handle
+        return handle
+
+    def generate_hessian_function(self):
+        """Returns ``hessian(free, lagrange) -> ndarray``: the constraint part
+        of the Hessian of the Lagrangian, ``sum_k lagrange_k d2 con_k /
+        d free^2``, evaluated on the GPU, with ``lagrange`` ordered like
+        ``constraints(free)`` (defects ``j*(N-1) + i``, then the instance
+        constraints).  Values of the LOWER triangle as triplets, in the order
+        of :meth:`hessian_indices`; a ``(row, col)`` pair may repeat and the
+        matrix is the SUM of its triplets (IPOPT's convention and
+        ``scipy.sparse.coo_matrix``'s; not the last-write-wins of the
+        reference's Jacobian helper ``_coo_matrix``).  The result is a
+        persistent page-locked buffer that the next call overwrites.
+
+        ``free`` and ``lagrange`` may also be torch CUDA tensors; the result
+        is then a new CUDA tensor (nothing crosses PCIe)."""
+        handle = self._ensure_hessian()
+        hip = self._hip
+        result = hb.pinned_empty(handle.nnz)
+        ncon = self.num_constraints
+
+        def hessian(free, lagrange):
+            if hasattr(free, 'data_ptr'):
+                import torch
+                if tuple(free.shape) != (self.num_free,) or \
+                        tuple(lagrange.shape) != (ncon,):
+                    raise ValueError('free / lagrange have the wrong shape')
+                free = free.to(torch.float64).contiguous()
+                lagrange = lagrange.to(device=free.device,
+                                       dtype=torch.float64).contiguous()
+                self._sync_known(hip, None)
+                out = torch.empty(handle.nnz, dtype=torch.float64,
+                                  device=free.device)
+                torch.cuda.current_stream(free.device).synchronize()
+                handle.evaluate(free, lagrange, out, hb.DEVICE)
+                hip.synchronize()
+                return out
+            free = self._host_free(free)
+            lam = np.ascontiguousarray(lagrange, dtype=np.float64)
+            if lam.shape != (ncon,):
+                raise ValueError('lagrange must have shape ({},), got {}'
+                                 .format(ncon, lam.shape))
+            self._sync_known(hip, free)
+            handle.evaluate(free, lam, result, hb.HOST)
+            return result
+        hessian.handle = handle
+        return hessian
+
+    def hessian_indices(self):
+        """Row and column indices (int64, row >= col) of every value
+        ``generate_hessian_function`` returns, in that order, from the
+        device's closed form; pairs repeat (the matrix is the sum of its
+        triplets)."""
+        handle = self._ensure_hessian()
+        rows = np.empty(handle.nnz, dtype=np.int64)
+        cols = np.empty(handle.nnz, dtype=np.int64)
+        handle.indices(rows, cols, hb.HOST)
+        return rows, cols
+
+    def hessian_indices_closed_form(self):
+        """Row and column indices (int64) of the Hessian triplets from the
+        closed form on the host (lower triangle; a pair may repeat and the
+        matrix is the SUM of its triplets)."""
+        from .codegen.program import hessian_indices
+        idx = self.instance_constraints_free_index_map \
+            if self.num_instance_constraints else {}
+        return hessian_indices(self._build_hessian_program(),
+                               self.num_collocation_nodes,
+                               [idx[f] for f in self._inst_atoms])
 
     def generate_source(self):
         """HIP source of this problem's kernels and its launch metadata."""
@@ -2218,7 +2486,10 @@ class Problem(object):
                  bounds=None, show_compile_output=False, backend='hip',
                  eom_bounds=None, device=0, prune_zeros=False,
                  jacobian_layout='coo', deterministic=False,
-                 verify_builds=None, specialize_parameters=None):
+                 verify_builds=None, specialize_parameters=None,
+                 obj_hessian=None):
+        if obj_hessian is not None:
+            obj_hessian = self._check_obj_hessian(obj_hessian)
         if not sm.Matrix(equations_of_motion).has(sm.Derivative):
             raise ValueError('No time derivatives are present. The equations '
                              'of motion must be ordinary differential '
@@ -2261,6 +2532,60 @@ class Problem(object):
         self._generate_constraint_bound_arrays()
         self.obj_value = []
         self._nlp = None
+        if obj_hessian is not None:
+            self._install_hessian(obj_hessian)
+
+    @staticmethod
+    def _check_obj_hessian(obj_hessian):
+        """``(rows, cols, values)`` of the objective's Hessian: int64
+        indices of its lower triangle (``row >= col``), ``values`` a callable
+        of ``free`` or of ``(problem, free)``."""
+        try:
+            rows, cols, values = obj_hessian
+        except (TypeError, ValueError):
+            raise ValueError('obj_hessian must be (rows, cols, values).')
+        rows = np.asarray(rows, dtype=np.int64).ravel()
+        cols = np.asarray(cols, dtype=np.int64).ravel()
+        if rows.shape != cols.shape:
+            raise ValueError('obj_hessian rows and cols differ in length.')
+        if np.any(rows < cols):
+            raise ValueError('obj_hessian must hold the lower triangle only '
+                             '(row >= col).')
+        if not callable(values):
+            raise ValueError('obj_hessian values must be a callable of free '
+                             'or of (problem, free).')
+        return rows, cols, values
+
+    def _install_hessian(self, obj_hessian):
+        """Gives this instance the two callbacks cyipopt looks for --
+        ``hessianstructure()`` and ``hessian(free, lagrange, obj_factor)``:
+        the constraint triplets (``generate_hessian_function``, lower
+        triangle, summed duplicates), then the objective's.  Only an instance
+        built with ``obj_hessian`` has them; without them IPOPT keeps its
+        limited-memory quasi-Newton default."""
+        rows, cols, values = obj_hessian
+        if np.any((rows < 0) | (rows >= self.num_free)):
+            raise ValueError('obj_hessian indices out of range.')
+        col = self.collocator
+        con_hess = col.generate_hessian_function()
+        crows, ccols = col.hessian_indices()
+        structure = (np.concatenate((crows, rows)),
+                     np.concatenate((ccols, cols)))
+        nargs = values.__code__.co_argcount - len(values.__defaults__ or ()) \
+            if hasattr(values, '__code__') else 1
+        num_con = len(crows)
+
+        def hessianstructure():
+            return structure
+
+        def hessian(free, lagrange, obj_factor):
+            out = np.empty(num_con + len(rows))
+            out[:num_con] = con_hess(free, lagrange)
+            v = values(self, free) if nargs == 2 else values(free)
+            out[num_con:] = obj_factor*np.asarray(v, dtype=float)
+            return out
+        self.hessianstructure = hessianstructure
+        self.hessian = hessian
 
     bounds = property(lambda self: self._bounds)
     eom_bounds = property(lambda self: self._eom_bounds)
@@ -2465,6 +2790,9 @@ class ShardedProblem(Problem):
 
     def __init__(self, *args, group=None, root=0, torch_device=None,
                  **kwargs):
+        if kwargs.get('obj_hessian') is not None:
+            raise NotImplementedError('the Hessian is not sharded: '
+                                      'ShardedProblem takes no obj_hessian.')
         self._group, self._root, self._torch_device = group, root, \
             torch_device
         super().__init__(*args, **kwargs)

@@ -75,7 +75,7 @@ def _hipcc():
 #: translation units of libopty_hip.so (csrc/opty_internal.h says what is
 #: where) and of the build referee's own library
 RUNTIME_SOURCES = ('runtime.cpp', 'programs.cpp', 'host_scatter.cpp',
-                   'comm.cpp')
+                   'comm.cpp', 'hessian.cpp')
 REFEREE_SOURCES = ('referee.cpp',)
 REFEREE_PATH = os.path.join(_PKG, 'libopty_hip_referee.so')
 
@@ -387,6 +387,12 @@ class _MatDesc(ctypes.Structure):
         'waves_per_wg', 'num_uniform', 'device')]
 
 
+class _HessDesc(ctypes.Structure):
+    _fields_ = [('PH', ctypes.c_int32), ('nnz_inst', ctypes.c_int32),
+                ('strips', ctypes.c_int32), ('pattern', ctypes.c_void_p),
+                ('inst_rows', ctypes.c_void_p), ('inst_cols', ctypes.c_void_p)]
+
+
 class _ObjDesc(ctypes.Structure):
     _fields_ = [('N', ctypes.c_int64), ('n', ctypes.c_int32),
                 ('q', ctypes.c_int32), ('r', ctypes.c_int32),
@@ -488,6 +494,13 @@ _SIGNATURES = {
     'opty_hip_bcast_free': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32]),
     'opty_hip_gather_v': (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P,
                                          ctypes.c_int32, ctypes.c_int32]),
+    'opty_hip_hessian_create': (ctypes.c_int, [_P, ctypes.POINTER(_HessDesc),
+                                               ctypes.c_char_p,
+                                               ctypes.POINTER(_P)]),
+    'opty_hip_hessian_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_hessian_nnz': (ctypes.c_int64, [_P]),
+    'opty_hip_eval_hess': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    'opty_hip_hessian_indices': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32]),
     'opty_hip_abi_version': (ctypes.c_int, []),
     'opty_hip_device_count': (ctypes.c_int, []),
     'opty_hip_last_error': (ctypes.c_char_p, []),
@@ -734,6 +747,9 @@ class HipProblem(object):
         self.nnz = self._lib.opty_hip_nnz(self._h)
 
     def close(self):
+        # Hessian handles borrow this one: they go first
+        for dep in list(getattr(self, '_dependents', ())):
+            dep.release()
         if getattr(self, '_h', None):
             self._lib.opty_hip_destroy(self._h)
             self._h = None
@@ -1088,3 +1104,59 @@ class HipObjective(object):
         _check(self._lib.opty_hip_objective_eval(
             self._h, _ptr(free), ctypes.addressof(value), _ptr(grad), mem))
         return value.value
+
+
+class HipHessian(object):
+    """One ``opty_hip_hessian`` handle: the exact Hessian of the constraint
+    Lagrangian of a :class:`HipProblem`, whose device data it borrows.  When
+    the problem's C handle is replaced (:meth:`HipProblem.reload`) or closed,
+    this handle is released first and created again for the new one on the
+    next call."""
+
+    def __init__(self, problem, desc, hsaco_path):
+        self._lib = load_library()
+        self._problem = problem
+        self._desc = dict(desc)
+        self._pattern = np.ascontiguousarray(desc['pattern'],
+                                             dtype=np.int32).reshape(-1)
+        self._irows = np.ascontiguousarray(desc['inst_rows'], dtype=np.int64)
+        self._icols = np.ascontiguousarray(desc['inst_cols'], dtype=np.int64)
+        self._hsaco = hsaco_path
+        self._h = None
+        import weakref
+        deps = problem.__dict__.setdefault('_dependents', weakref.WeakSet())
+        deps.add(self)
+        self._handle()
+        self.nnz = self._lib.opty_hip_hessian_nnz(self._h)
+
+    def _handle(self):
+        if self._h is None:
+            if not getattr(self._problem, '_h', None):
+                raise HipBackendError('the problem handle is closed')
+            d = _HessDesc(PH=self._desc['PH'],
+                          nnz_inst=self._desc['nnz_inst'],
+                          strips=self._desc['strips'],
+                          pattern=_ptr(self._pattern),
+                          inst_rows=_ptr(self._irows),
+                          inst_cols=_ptr(self._icols))
+            h = _P()
+            _check(self._lib.opty_hip_hessian_create(
+                self._problem._h, ctypes.byref(d), self._hsaco.encode(),
+                ctypes.byref(h)))
+            self._h = h
+        return self._h
+
+    def release(self):
+        if getattr(self, '_h', None):
+            self._lib.opty_hip_hessian_destroy(self._h)
+            self._h = None
+
+    __del__ = release
+
+    def evaluate(self, free, lagrange, hess, mem):
+        _check(self._lib.opty_hip_eval_hess(self._handle(), _ptr(free),
+                                            _ptr(lagrange), _ptr(hess), mem))
+
+    def indices(self, rows, cols, mem):
+        _check(self._lib.opty_hip_hessian_indices(self._handle(), _ptr(rows),
+                                                  _ptr(cols), mem))
