@@ -153,14 +153,28 @@ typedef struct opty_hip_desc {
                              launch plan's tuner or the printer's estimate);
                              classes = jac_wgs_per_block                      */
     float fused_class_cost[OPTY_HIP_MAX_CLASSES];
+    int32_t var_jac_wgs_per_block; /* > 0: the module carries the RESTRICTED
+                             flavour of the Jacobian kernels, opty_jac_var and
+                             opty_conjac_var, which write only the 128-byte
+                             lines of a block that hold an entry that can
+                             change between two evaluations (see
+                             opty_hip_output_register); workgroups per
+                             64-node block of opty_jac_var.  0: no such
+                             kernels (nothing worth skipping, another layout,
+                             or a build that spilled): registration is
+                             accepted and has no effect                       */
+    int32_t var_jac_waves_per_wg;  /* waves per such workgroup                */
+    int32_t var_fused_wgs_per_block; /* the same for opty_conjac_var          */
+    int32_t var_fused_waves_per_wg;
 } opty_hip_desc;
 
 /* Version of this header's structs and signatures; opty_hip_abi_version()
  * returns the one the library was built from.  A client built against another
- * version must not call the library: the descriptor grew in 5, 6 and 7, and
+ * version must not call the library: the descriptor grew in 5, 6, 7 and 8
+ * (8: the restricted kernels' geometry, opty_hip_output_*), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
-#define OPTY_HIP_ABI_VERSION 7
+#define OPTY_HIP_ABI_VERSION 8
 int opty_hip_abi_version(void);
 
 /* (The build verification's device side -- register poisoner, instruction
@@ -415,11 +429,45 @@ int opty_hip_time_eval_shard(opty_hip_problem *p, int32_t what,
                              int64_t node_begin, int64_t node_end,
                              int32_t iters, float *ms_per_iter);
 
+/* Registered device outputs.  The OWNER of a device Jacobian buffer that
+ * keeps what the library wrote into it -- nobody else writes to it between two
+ * evaluations -- says so: opty_hip_output_register(p, jac, node_begin,
+ * node_end) for the buffer that opty_hip_eval_shard (or, with the whole node
+ * range [0, N-1), opty_hip_eval_jac / opty_hip_eval_con_jac with device
+ * memory) is given for that node range.  Two thirds of a multibody block are
+ * the same at every node and every call (structural zeros, +-1, +-1/h,
+ * products of known masses and lengths): the first evaluation into a
+ * registered buffer writes everything, the following ones launch the module's
+ * restricted kernels (opty_hip_desc.var_*), which write only the 128-byte
+ * lines that hold an entry that can change; the bytes in between are NOT
+ * touched, so the buffer is read-only for its owner between calls.  Everything
+ * is written again after whatever can change a node-invariant entry or leaves
+ * the buffer's contents in doubt: opty_hip_set_known_parameters,
+ * opty_hip_set_interval, opty_hip_set_block_pattern, opty_hip_set_segments, a
+ * reload of the module, an evaluation of ANOTHER node range into the buffer,
+ * an evaluation that returned an error, opty_hip_output_invalidate (jac ==
+ * NULL: every registered buffer of the handle; what an owner calls after
+ * writing to the buffer itself).  The registration is the owner's word: the
+ * library never infers persistence from an address it has seen before, and an
+ * unregistered pointer is always written whole.  Unregister before the memory
+ * is released.  OPTY_HIP_DENSE_OUTPUT=1 in the environment (read once) turns
+ * the restricted path off: registered buffers are written whole, too.
+ * Registering a registered address again replaces its node range;
+ * unregistering or invalidating an address that is not registered is an
+ * error.  At most 64 buffers per handle. */
+int opty_hip_output_register(opty_hip_problem *p, double *jac,
+                             int64_t node_begin, int64_t node_end);
+int opty_hip_output_unregister(opty_hip_problem *p, double *jac);
+int opty_hip_output_invalidate(opty_hip_problem *p, double *jac);
+
 /* What the entry points launch for a launch of `node_count` constraint nodes
- * (opty_hip_desc.routing): *calibrated = 1 when the handle has measured that
- * launch size on its device (ms3[0..2] = per-launch ms of opty_conjac,
- * opty_con, opty_jac as measured), 0 when the launch plan's flags are still
- * in force; *fused_loses = 1: OPTY_HIP_EVAL_FUSED issues opty_con + opty_jac;
+ * (opty_hip_desc.routing): bit 0 of *calibrated is set when the handle has
+ * measured that launch size on its device (ms3[0..2] = per-launch ms of
+ * opty_conjac, opty_con, opty_jac as measured), clear when the launch plan's
+ * flags are still in force; bit 1 is set when the LAST Jacobian launch of
+ * that size was served by the restricted flavour (opty_conjac_var /
+ * opty_jac_var into a registered output) -- the flags and times are then
+ * that flavour's, which is calibrated on its own; *fused_loses = 1: OPTY_HIP_EVAL_FUSED issues opty_con + opty_jac;
  * *jac_via_fused = 1: OPTY_HIP_EVAL_JAC launches opty_conjac.  Any output
  * pointer may be null.  The reference calls its two callbacks separately
  * (opty/direct_collocation.py:498-562): whichever kernel serves them, the

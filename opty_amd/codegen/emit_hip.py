@@ -33,9 +33,11 @@ Jacobian has thousands of temporaries.  The printer therefore
 """
 
 import hashlib
+import math
 import os
 
 from . import ir
+from .program import line_owner_ranges
 
 WAVE = 64
 TS = 65
@@ -95,6 +97,10 @@ FUSED_STRIPS_PER_SQRT_ENTRY = 0.286
 #: constraint stores past the caches (between the 70 MB of N = 4*10^5, still
 #: fine with plain stores, and the 176 MB of N = 10^6)
 CON_CACHE_BYTES = 128 << 20
+
+#: largest block (stored entries per node) that gets the restricted kernels
+#: unless asked for (EmitOptions.restricted)
+RESTRICTED_MAX_P = 2048
 
 #: doubles between the end of a launch's Jacobian values and the wave records
 #: of ``EmitOptions.trace``
@@ -197,7 +203,21 @@ class EmitOptions(object):
                  park=0, park_live=215, park_spread=0, strips=None,
                  fused_strips=None,
                  fused_order=None, deterministic=0, class_cost=None,
-                 fused_class_cost=None, share_rcp=0, publish=0):
+                 fused_class_cost=None, share_rcp=0, publish=0,
+                 var_groups=None, var_fused_groups=None, restricted=None):
+        # the restricted flavour of the Jacobian kernels (emit_module): None
+        # = automatic -- blocks of up to RESTRICTED_MAX_P entries: the two
+        # extra kernels of a larger block (24-link systems: 5 100 entries,
+        # minutes of hipcc per kernel and module) would make every build
+        # of it half as long again; 1 asks for them whatever the size, 0
+        # never
+        self.restricted = None if restricted is None else int(restricted)
+        # strips of the restricted kernels (opty_jac_var / opty_conjac_var:
+        # the kept spans of the block only, emit_module); None = as many as
+        # give the strips the width the full kernels' strips have
+        self.var_groups = None if var_groups is None else int(var_groups)
+        self.var_fused_groups = None if var_fused_groups is None \
+            else int(var_fused_groups)
         # 1 (r06, launches that under-fill the chip -- node shards): the
         # waves of a block form ONE workgroup and evaluate the block's
         # isomorphic sub-models (codegen/isomorph.py: the musculotendon
@@ -454,7 +474,13 @@ class EmitOptions(object):
                  else ' fused_order=%s' % self.fused_order) +
                 (' deterministic=1' if self.deterministic else '') +
                 (' share_rcp=1' if self.share_rcp else '') +
-                (' publish=1' if self.publish else ''))
+                (' publish=1' if self.publish else '') +
+                ('' if self.restricted is None
+                 else ' restricted=%d' % self.restricted) +
+                ('' if self.var_groups is None
+                 else ' var_groups=%d' % self.var_groups) +
+                ('' if self.var_fused_groups is None
+                 else ' var_fused_groups=%d' % self.var_fused_groups))
 
 
 def _lit(v):
@@ -990,6 +1016,10 @@ class _ModuleWriter(object):
         self._pub_rows = {}         # published node -> LDS row, kernel in print
 
     # -- leaves -------------------------------------------------------------
+    #: True while a restricted kernel is printed: its last strip may end
+    #: inside the block and still stage the next node's first entries
+    _restricted = False
+
     def _is_vec_input(self, i):
         return self.dag.op[i] == ir.INPUT and \
             self.dag.args[i][0] in ('cur', 'adj')
@@ -1382,6 +1412,39 @@ class _ModuleWriter(object):
             return [[rg] for rg in self._auto_work]
         return split(self._auto[1])
 
+    def restricted_ranges(self):
+        """Line-owner ranges of the restricted kernels
+        (``program.line_owner_ranges``), or ``[]`` when this module has none:
+        nothing worth skipping, a layout other than whole node-major blocks
+        flushed by lines, or printer options whose machinery the restricted
+        kernels do not carry (list schedules, publication, LDS parking,
+        interleaved strips, traces, the strip-dropping ablations)."""
+        o = self.o
+        if not self.line_mode() or self.csr() or \
+                getattr(self.p, 'layout', 'coo') != 'coo' or \
+                getattr(self.p, 'pruned', False) or \
+                o.publish or o.park or o.interleave or o.trace or o.pad or \
+                'list' in (o.order, o.fused_order) or \
+                o.ablate not in (None, 'store_only', 'compute_only') or \
+                o.restricted == 0 or \
+                (o.restricted is None and self.p.P > RESTRICTED_MAX_P):
+            return []
+        return line_owner_ranges(self.p)
+
+    def restricted_strips(self, ranges, count):
+        """``count`` strips (at least one per range) cut INSIDE the owner
+        ranges ``[(lo, hi), ...]`` at multiples of a 16-entry line, as equal
+        in width as that allows; one strip per wave."""
+        total = sum(hi - lo for lo, hi in ranges)
+        count = max(len(ranges), int(count))
+        groups = []
+        for lo, hi in ranges:
+            units = max(1, (hi - lo)//16)
+            n = max(1, min(units, int(round(count*(hi - lo)/float(total)))))
+            b = [lo + ((k*units)//n)*16 for k in range(n)] + [hi]
+            groups += [[(b[k], b[k + 1])] for k in range(n)]
+        return groups
+
     def explicit_strips(self, spec):
         """``'96:160;160:348+0:96'`` -> ``[[(96, 160)], [(160, 348), (0,
         96)]]``, checked: boundaries on 16-entry lines, every entry once."""
@@ -1747,7 +1810,7 @@ class _ModuleWriter(object):
         at the wave's first node there, ``b0`` is its line phase."""
         P = self.p.P if width is None else width
         K = self.o.chunk
-        if e1 < P:
+        if e1 < P and not self._restricted:
             assert e1 + 15 <= P, 'last entry range must be >= 16 wide'
         for c0 in range(e0, e1 + 15, K):
             c1 = min(c0 + K, e1 + 15)
@@ -2691,6 +2754,7 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
     # waves ride in the shadow of the store-bound Jacobian waves.  Where the
     # ARITHMETIC sets the pace instead, a constraint row is evaluated by the
     # Jacobian wave that computes most of its sub-expressions anyway.
+    detached_sets = con_sets
     attached, con_sets = _attach_constraint_rows(prog, w, opts, fused_jac,
                                                  con_sets)
     con_groups = [[(0, 0)]]*len(con_sets)
@@ -2734,6 +2798,36 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
             order=opts.fused_order if key == 'conjac' else None)
         parts += [src, '']
         kernels[key] = meta
+    # The restricted flavour of the two Jacobian kernels, for outputs whose
+    # owner keeps them between evaluations (opty_hip_output_register): only
+    # the lines that hold an entry which can change are written, the strips
+    # are cut inside the kept spans; the entries' code is the full kernels'.
+    # The constraint rows ride in waves of their own.
+    var_ranges = w.restricted_ranges()
+    var_groups = var_fused = None
+    if var_ranges:
+        # (rounded up: a restricted strip is never wider than a full one,
+        # whose register budget it shares)
+        share = sum(hi - lo for lo, hi in var_ranges)/float(prog.P)
+        var_groups = w.restricted_strips(
+            var_ranges, opts.var_groups if opts.var_groups is not None
+            else int(math.ceil(len(groups)*share)))
+        var_fused = w.restricted_strips(
+            var_ranges, opts.var_fused_groups
+            if opts.var_fused_groups is not None
+            else int(math.ceil(len(fused_jac)*share)))
+        w._restricted = True
+        for key, name, grp, cons, nt in (
+                ('jac_var', 'opty_jac_var', var_groups,
+                 [[] for _ in var_groups], False),
+                ('conjac_var', 'opty_conjac_var',
+                 list(var_fused) + [[(0, 0)]]*len(detached_sets),
+                 [[] for _ in var_fused] + detached_sets, nt_fused)):
+            src, meta = w.kernel(name, grp, cons, opts.waves, nt,
+                                 inst_lines=folded, order='block')
+            parts += [src, '']
+            kernels[key] = meta
+        w._restricted = False
     if prog.inst_con_out:
         src, meta = w.inst_kernel()
         parts += [src, '']
@@ -2760,6 +2854,11 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
                 inst_folded=bool(folded),
                 con_attached=bool(any(attached)),
                 sha=hashlib.sha256(source.encode()).hexdigest())
+    if var_ranges:
+        meta['restricted'] = dict(
+            owner_ranges=[list(rg) for rg in var_ranges],
+            groups=[[list(rg) for rg in grp] for grp in var_groups],
+            fused_groups=[[list(rg) for rg in grp] for grp in var_fused])
     if w._plans:
         meta['plans'] = w._plans
     if literals:

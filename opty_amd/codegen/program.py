@@ -461,6 +461,73 @@ def varying_entries(prog):
     return [e for e, node in enumerate(prog.jac_out) if not is_static(node)]
 
 
+#: shortest run of node-invariant entries that the restricted Jacobian
+#: kernels skip: a run of L entries holds at least (L - 15)//16 whole
+#: 128-byte lines of the flat output whatever the line phase of the node's
+#: row, so 32 is the shortest run that removes a whole line in every phase
+SKIP_MIN_RUN = 32
+
+
+def kept_spans(prog, min_run=SKIP_MIN_RUN):
+    """The entry spans ``[(a, b), ...]`` of a block that an evaluation into a
+    buffer which still holds the previous evaluation's values has to write
+    again: the complement of the maximal runs of node-invariant entries
+    (:func:`varying_entries`' complement) that are at least ``min_run`` long.
+    Shorter static gaps stay inside a span (they are written as always, from
+    their literal / table values: the stores stay whole lines).  Blocks
+    follow each other in memory, so the run behind the last varying entry
+    continues in the next node's first entries: it is skipped when the two
+    parts together are long enough AND the first varying entry has 15
+    static entries of its own block in front of it (the line that holds it
+    then starts in the same block); otherwise the first span starts at entry
+    0 and the last one ends at P.  A block without varying entries, or
+    without a run worth skipping, gives ``[(0, P)]``: nothing is skipped.
+    For the 10-link pendulum: ``[(496, 988)]`` of 990 entries."""
+    P = prog.P
+    var = varying_entries(prog)
+    if not var:
+        return [(0, P)]
+    spans, a = [], var[0]
+    for prev, e in zip(var, var[1:]):
+        if e - prev - 1 >= min_run:
+            spans.append((a, prev + 1))
+            a = e
+    spans.append((a, var[-1] + 1))
+    wrap = (P - 1 - var[-1]) + var[0]
+    if wrap < min_run or var[0] < 15:
+        spans[0] = (0, spans[0][1])
+        spans[-1] = (spans[-1][0], P)
+    return spans
+
+
+def line_owner_ranges(prog, spans=None):
+    """What the restricted kernels make of :func:`kept_spans`: a wave owns
+    the 128-byte lines whose FIRST entry lies in its range, and the line that
+    holds entry ``a`` may start up to 15 entries earlier -- so the span ``(a,
+    b)`` becomes the owner range ``(a - 15 rounded down to a multiple of 16,
+    b)``; the entries staged are those of ``[lo, b + 15)`` (past P: the next
+    node's first entries).  Empty when nothing is skipped."""
+    spans = kept_spans(prog) if spans is None else spans
+    if spans == [(0, prog.P)]:
+        return []
+    return [(max(0, (a - 15)//16*16), b) for a, b in spans]
+
+
+def kept_lines_per_node(prog, spans=None):
+    """``(kept, all)``: 128-byte lines of the flat output per node, averaged
+    over the 16 line phases a node's row can start at, that hold at least one
+    entry of a kept span / at least one entry at all (P/16)."""
+    P = prog.P
+    spans = kept_spans(prog) if spans is None else spans
+    kept = 0
+    for phase in range(16):
+        lines = set()
+        for a, b in spans:
+            lines |= {(phase + e)//16 for e in range(a, b)}
+        kept += len(lines)
+    return kept/16.0, P/16.0
+
+
 def varying_copies(prog):
     """Splits :func:`varying_entries` into the entries that have to be
     evaluated / moved and the ones that are *the same expression* as an

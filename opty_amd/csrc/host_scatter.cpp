@@ -1333,6 +1333,7 @@ int opty_hip_set_segments(opty_hip_problem *p, const int32_t *order,
                       hipMemcpyHostToDevice));
     p->have_segments = true;
     p->static_valid = p->shard_valid = false;
+    p->invalidate_outputs();
     return 0;
 }
 

@@ -92,18 +92,33 @@ struct Schedule {
 // the device the handle lives on (opty_hip_desc.routing, calibrate_route).
 struct Route {
     long long nblk = -1;
+    bool var = false;       // the restricted flavour (opty_*_var kernels)
     bool fused_loses = false, jac_via_fused = false;
     float ms_fused = 0.f, ms_con = 0.f, ms_jac = 0.f;   // per launch
+};
+
+// A device Jacobian buffer whose owner keeps what the library wrote into it
+// (opty_hip_output_register): `valid` = it holds a whole evaluation of the
+// node range [begin, end) with the handle's present node-invariant values.
+struct RegisteredOutput {
+    double *jac = nullptr;
+    long long begin = 0, end = 0;
+    bool valid = false;
 };
 
 struct opty_hip_problem {
     std::vector<Schedule> sched_jac, sched_fused;
     std::vector<Route> routes;
+    std::vector<RegisteredOutput> outputs;
+    // flavour of the last Jacobian launch per launch size (opty_hip_routing)
+    std::vector<std::pair<long long, bool>> served;
+    void invalidate_outputs() { for (auto &o : outputs) o.valid = false; }
     hipEvent_t ev_cal0 = nullptr, ev_cal1 = nullptr;
     opty_hip_desc d{};
     hipModule_t module = nullptr;
     hipFunction_t k_con = nullptr, k_jac = nullptr, k_conjac = nullptr,
-                  k_inst = nullptr, k_uni = nullptr;
+                  k_inst = nullptr, k_uni = nullptr, k_jac_var = nullptr,
+                  k_conjac_var = nullptr;
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipStream_t copy_stream = nullptr;  // device-to-host side of a pipeline
     hipStream_t copy_stream2 = nullptr; // ... its chunks alternate between two

@@ -351,7 +351,7 @@ int time_issue(opty_hip_problem *p, Fn fn, float *ms_out) {
 // item 2: the plan file's flags were measured on another box, and were wrong
 // on the driver's for two problems).
 int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
-                    double *jac, const NodeRange &rg, Route *out) {
+                    double *jac, const NodeRange &rg, bool var, Route *out) {
     if (!p->ev_cal0) {
         HIP_TRY(hipEventCreate(&p->ev_cal0));
         HIP_TRY(hipEventCreate(&p->ev_cal1));
@@ -363,7 +363,13 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
         con = p->d_con_scratch + rg.begin;
         cr.con_stride = p->ncon_nodes();
     }
+    // `var`: the restricted flavour (the caller vouches that `jac` holds a
+    // whole evaluation of this node range: its launches leave the
+    // node-invariant lines alone)
     auto fused = [&] {
+        if (var)
+            return launch(p, p->k_conjac_var, p->d.var_fused_wgs_per_block,
+                          64*p->d.var_fused_waves_per_wg, free_, con, jac, cr);
         return launch(p, p->k_conjac, p->d.fused_wgs_per_block,
                       64*p->d.fused_waves_per_wg, free_, con, jac, cr, false,
                       p->d.fused_persist, &p->sched_fused,
@@ -374,6 +380,10 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
                       64*p->d.con_waves_per_wg, free_, con, nullptr, cr);
     };
     auto jack = [&] {
+        if (var)
+            return launch(p, p->k_jac_var, p->d.var_jac_wgs_per_block,
+                          64*p->d.var_jac_waves_per_wg, free_, nullptr, jac,
+                          cr);
         return launch(p, p->k_jac, p->d.jac_wgs_per_block,
                       64*p->d.jac_waves_per_wg, free_, nullptr, jac, cr,
                       false, p->d.jac_persist, &p->sched_jac,
@@ -381,6 +391,7 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
     };
     Route r;
     r.nblk = (rg.end - rg.begin + 63)/64;
+    r.var = var;
     if (int rc = time_issue(p, fused, &r.ms_fused)) return rc;
     if (int rc = time_issue(p, conk, &r.ms_con)) return rc;
     if (int rc = time_issue(p, jack, &r.ms_jac)) return rc;
@@ -394,10 +405,11 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
                   : (r.ms_fused < r.ms_jac*0.99f - 3e-4f));
     static const bool trace = getenv("OPTY_HIP_TRACE") != nullptr;
     if (trace)
-        fprintf(stderr, "opty_hip: routing of %lld-block launches: opty_conjac "
-                "%.4f ms, opty_con %.4f + opty_jac %.4f = %.4f ms -> "
-                "fused_loses %d (plan %d), jac_via_fused %d (plan %d)\n",
-                r.nblk, r.ms_fused, r.ms_con, r.ms_jac, pair,
+        fprintf(stderr, "opty_hip: routing of %lld-block launches%s: "
+                "opty_conjac %.4f ms, opty_con %.4f + opty_jac %.4f = %.4f ms "
+                "-> fused_loses %d (plan %d), jac_via_fused %d (plan %d)\n",
+                r.nblk, var ? " (restricted kernels)" : "", r.ms_fused,
+                r.ms_con, r.ms_jac, pair,
                 (int)r.fused_loses, (int)plan_loses, (int)r.jac_via_fused,
                 (int)plan_via);
     *out = r;
@@ -407,26 +419,102 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
 // The route of the launch size of `rg`; measured at its first use.  *out
 // stays null when it cannot be measured (no Jacobian buffer: never asked).
 int route_for(opty_hip_problem *p, const double *free_, double *con,
-              double *jac, const NodeRange &rg, const Route **out) {
+              double *jac, const NodeRange &rg, bool var, const Route **out) {
     const long long nblk = (rg.end - rg.begin + 63)/64;
     for (const Route &r : p->routes)
-        if (r.nblk == nblk) {
+        if (r.nblk == nblk && r.var == var) {
             *out = &r;
             return 0;
         }
     if (!jac || nblk == 0) return 0;
     Route r;
-    if (int rc = calibrate_route(p, free_, con, jac, rg, &r)) return rc;
+    if (int rc = calibrate_route(p, free_, con, jac, rg, var, &r)) return rc;
     if (p->routes.size() >= 16) p->routes.erase(p->routes.begin());
     p->routes.push_back(r);
     *out = &p->routes.back();
     return 0;
 }
 
+bool dense_output() {
+    // OPTY_HIP_DENSE_OUTPUT=1: registered outputs are written whole as well
+    // (the A/B lever of the restricted kernels; in the spirit of
+    // OPTY_HOST_DENSE=1 of the host path)
+    static const bool dense = [] {
+        const char *e = getenv("OPTY_HIP_DENSE_OUTPUT");
+        return e && *e && strcmp(e, "0") != 0;
+    }();
+    return dense;
+}
+
+RegisteredOutput *find_output(opty_hip_problem *p, const double *jac) {
+    if (!jac) return nullptr;
+    for (RegisteredOutput &o : p->outputs)
+        if (o.jac == jac) return &o;
+    return nullptr;
+}
+
+// The registered output an evaluation of `rg` into `jac` may treat as still
+// holding its node-invariant entries (null: write everything).
+RegisteredOutput *restricted_output(opty_hip_problem *p, int what,
+                                    const double *jac, const NodeRange &rg) {
+    if (what == OPTY_HIP_EVAL_CON || !p->k_jac_var || dense_output())
+        return nullptr;
+    RegisteredOutput *o = find_output(p, jac);
+    return o && o->valid && o->begin == rg.begin && o->end == rg.end
+        ? o : nullptr;
+}
+
+static int eval_device_impl(opty_hip_problem *p, int what,
+                            const double *free_, double *con, double *jac,
+                            const NodeRange &rg, bool with_inst, bool var);
+
+// Evaluations into a registered output (opty_hip_output_register): the
+// restricted kernels when the buffer holds a whole evaluation of the same
+// node range, else everything -- after which it does.  The entry is invalid
+// while the launches are being issued, so that an error return leaves it
+// invalid; stream order makes validity at enqueue time sufficient (all
+// launches of a handle are ordered: order_streams).
 int eval_device(opty_hip_problem *p, int what, const double *free_,
                 double *con, double *jac, const NodeRange &rg,
                 bool with_inst) {
-    const int S = p->d.jac_wgs_per_block, T = 64*p->d.jac_waves_per_wg;
+    if (what == OPTY_HIP_EVAL_CON || p->outputs.empty())
+        return eval_device_impl(p, what, free_, con, jac, rg, with_inst,
+                                false);
+    const bool var = restricted_output(p, what, jac, rg) != nullptr;
+    RegisteredOutput *o = find_output(p, jac);
+    const bool match = o && o->begin == rg.begin && o->end == rg.end;
+    if (o) o->valid = false;
+    const int rc = eval_device_impl(p, what, free_, con, jac, rg, with_inst,
+                                    var);
+    if (rc == 0 && match) o->valid = true;
+    return rc;
+}
+
+static int eval_device_impl(opty_hip_problem *p, int what,
+                            const double *free_, double *con, double *jac,
+                            const NodeRange &rg, bool with_inst, bool var) {
+    // the two Jacobian kernels of the flavour that serves this launch
+    const hipFunction_t k_jac = var ? p->k_jac_var : p->k_jac;
+    const hipFunction_t k_conjac = var ? p->k_conjac_var : p->k_conjac;
+    const int S = var ? p->d.var_jac_wgs_per_block : p->d.jac_wgs_per_block,
+              T = 64*(var ? p->d.var_jac_waves_per_wg
+                          : p->d.jac_waves_per_wg);
+    const int FS = var ? p->d.var_fused_wgs_per_block
+                       : p->d.fused_wgs_per_block,
+              FT = 64*(var ? p->d.var_fused_waves_per_wg
+                           : p->d.fused_waves_per_wg);
+    const int jac_persist = var ? 0 : p->d.jac_persist,
+              fused_persist = var ? 0 : p->d.fused_persist;
+    if (what != OPTY_HIP_EVAL_CON) {
+        const long long nblk = (rg.end - rg.begin + 63)/64;
+        bool seen = false;
+        for (auto &sv : p->served)
+            if (sv.first == nblk) { sv.second = var; seen = true; }
+        if (!seen) {
+            if (p->served.size() >= 16) p->served.erase(p->served.begin());
+            p->served.emplace_back(nblk, var);
+        }
+    }
     if (int rc = order_streams(p)) return rc;
     // Node-invariant sub-expressions: recomputed only when their inputs can
     // have changed (always, if they read unknown parameters / h from `free`).
@@ -454,7 +542,7 @@ int eval_device(opty_hip_problem *p, int what, const double *free_,
         routing_enabled() &&
         (what == OPTY_HIP_EVAL_FUSED || what == OPTY_HIP_EVAL_JAC)) {
         const Route *rt = nullptr;
-        if (int rc = route_for(p, free_, con, jac, rg, &rt)) return rc;
+        if (int rc = route_for(p, free_, con, jac, rg, var, &rt)) return rc;
         if (rt) {
             fused_loses = rt->fused_loses;
             jac_via_fused = rt->jac_via_fused;
@@ -485,10 +573,9 @@ int eval_device(opty_hip_problem *p, int what, const double *free_,
         if (int rc = ensure(&p->d_con_scratch, (size_t)p->num_con()))
             return rc;
         NodeRange sr{rg.begin, rg.end, p->ncon_nodes()};
-        if (int rc = launch(p, p->k_conjac, p->d.fused_wgs_per_block,
-                            64*p->d.fused_waves_per_wg, free_,
+        if (int rc = launch(p, k_conjac, FS, FT, free_,
                             p->d_con_scratch + rg.begin, jac, sr, folded,
-                            p->d.fused_persist, &p->sched_fused,
+                            fused_persist, &p->sched_fused,
                             p->d.fused_class_cost))
             return rc;
         if (tails && !folded)
@@ -503,14 +590,13 @@ int eval_device(opty_hip_problem *p, int what, const double *free_,
                             folded))
             return rc;
     if (what == OPTY_HIP_EVAL_JAC || what == OPTY_HIP_EVAL_PAIR)
-        if (int rc = launch(p, p->k_jac, S, T, free_, nullptr, jac, rg,
-                            folded, p->d.jac_persist, &p->sched_jac,
+        if (int rc = launch(p, k_jac, S, T, free_, nullptr, jac, rg,
+                            folded, jac_persist, &p->sched_jac,
                             p->d.jac_class_cost))
             return rc;
     if (what == OPTY_HIP_EVAL_FUSED)
-        if (int rc = launch(p, p->k_conjac, p->d.fused_wgs_per_block,
-                            64*p->d.fused_waves_per_wg, free_, con, jac, rg,
-                            folded, p->d.fused_persist, &p->sched_fused,
+        if (int rc = launch(p, k_conjac, FS, FT, free_, con, jac, rg,
+                            folded, fused_persist, &p->sched_fused,
                             p->d.fused_class_cost))
             return rc;
     if (tails && !folded) {
@@ -793,6 +879,20 @@ int opty_hip_create(const opty_hip_desc *desc, const char *code_object_path,
          desc->fused_wgs_per_block > OPTY_HIP_MAX_CLASSES))
         return fail("a list schedule takes at most %d strip classes",
                     OPTY_HIP_MAX_CLASSES);
+    const bool has_var = desc->var_jac_wgs_per_block != 0 ||
+        desc->var_fused_wgs_per_block != 0;
+    if (has_var && (desc->var_jac_wgs_per_block < 1 ||
+                    desc->var_jac_waves_per_wg < 1 ||
+                    desc->var_jac_waves_per_wg > 16 ||
+                    desc->var_fused_wgs_per_block < 1 ||
+                    desc->var_fused_waves_per_wg < 1 ||
+                    desc->var_fused_waves_per_wg > 16 ||
+                    desc->layout != OPTY_HIP_LAYOUT_COO))
+        return fail("bad geometry of the restricted kernels (%d x %d, %d x "
+                    "%d; node-major layout only)",
+                    desc->var_jac_wgs_per_block, desc->var_jac_waves_per_wg,
+                    desc->var_fused_wgs_per_block,
+                    desc->var_fused_waves_per_wg);
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
         return fail("no HIP device is visible: the HIP backend has no CPU "
@@ -815,6 +915,8 @@ int opty_hip_create(const opty_hip_desc *desc, const char *code_object_path,
         {"opty_conjac", &p->k_conjac, true},
         {"opty_inst", &p->k_inst, desc->num_inst > 0},
         {"opty_uni", &p->k_uni, desc->num_uniform > 0},
+        {"opty_jac_var", &p->k_jac_var, has_var},
+        {"opty_conjac_var", &p->k_conjac_var, has_var},
     };
     for (auto &k : ks) {
         if (!k.required) continue;
@@ -910,6 +1012,7 @@ int opty_hip_set_known_parameters(opty_hip_problem *p, const double *values,
     HIP_TRY(hipStreamSynchronize(sync_target(p->stream)));
     p->uni_dirty = true;
     p->static_valid = p->shard_valid = false;   // invariant entries change
+    p->invalidate_outputs();
     p->have_params = true;
     return 0;
 }
@@ -923,6 +1026,7 @@ int opty_hip_set_interval(opty_hip_problem *p, double h) {
     p->have_h = true;
     p->uni_dirty = true;
     p->static_valid = p->shard_valid = false;
+    p->invalidate_outputs();
     return 0;
 }
 
@@ -973,6 +1077,7 @@ int opty_hip_set_instance_indices(opty_hip_problem *p,
 
 int opty_hip_set_block_pattern(opty_hip_problem *p, const int32_t *jk) {
     if (!p || !jk) return fail("null argument");
+    p->invalidate_outputs();
     if (int rc = use_device(p)) return rc;
     for (int e = 0; e < p->d.P; ++e)
         if (jk[2*e] < 0 || jk[2*e] >= p->d.M || jk[2*e + 1] < 0 ||
@@ -1152,12 +1257,22 @@ static int time_impl(opty_hip_problem *p, int32_t what, const double *free_,
                                 nullptr, rg)) return rc;
         p->uni_dirty = false;
     }
+    // a registered output that does not hold a whole evaluation yet gets one
+    // first: the timed launches are then all of the flavour the entry points
+    // serve it with from here on (the same decision as eval_device's)
+    if (what != OPTY_HIP_EVAL_CON && p->k_jac_var && !dense_output()) {
+        const RegisteredOutput *o = find_output(p, jac);
+        if (o && !o->valid && o->begin == rg.begin && o->end == rg.end)
+            if (int rc = eval_device(p, what, free_, con, jac, rg, with_inst))
+                return rc;
+    }
     // ... and the one-off calibration of the routing of this launch size
     if ((p->d.routing & OPTY_HIP_ROUTE_CALIBRATE) && routing_enabled() &&
         !(p->d.routing & ~OPTY_HIP_ROUTE_CALIBRATE) &&
         (what == OPTY_HIP_EVAL_FUSED || what == OPTY_HIP_EVAL_JAC)) {
+        const bool var = restricted_output(p, what, jac, rg) != nullptr;
         const Route *rt = nullptr;
-        if (int rc = route_for(p, free_, con, jac, rg, &rt)) return rc;
+        if (int rc = route_for(p, free_, con, jac, rg, var, &rt)) return rc;
     }
     HIP_TRY(hipEventRecord(p->ev0, p->stream));
     for (int it = 0; it < iters; ++it)
@@ -1214,22 +1329,68 @@ int opty_hip_time_eval_shard(opty_hip_problem *p, int32_t what,
                      ms_per_iter);
 }
 
+int opty_hip_output_register(opty_hip_problem *p, double *jac,
+                             int64_t node_begin, int64_t node_end) {
+    if (!p) return fail("null handle");
+    if (!jac) return fail("null buffer");
+    if (node_begin < 0 || node_end < node_begin ||
+        node_end > p->ncon_nodes())
+        return fail("output range [%lld, %lld) outside the %lld constraint "
+                    "nodes", (long long)node_begin, (long long)node_end,
+                    (long long)p->ncon_nodes());
+    RegisteredOutput *o = find_output(p, jac);
+    if (!o) {
+        if (p->outputs.size() >= 64)
+            return fail("at most 64 registered outputs per handle");
+        p->outputs.emplace_back();
+        o = &p->outputs.back();
+    }
+    o->jac = jac;
+    o->begin = node_begin;
+    o->end = node_end;
+    o->valid = false;
+    return 0;
+}
+
+int opty_hip_output_unregister(opty_hip_problem *p, double *jac) {
+    if (!p) return fail("null handle");
+    RegisteredOutput *o = find_output(p, jac);
+    if (!o) return fail("output %p is not registered", (void *)jac);
+    p->outputs.erase(p->outputs.begin() + (o - p->outputs.data()));
+    return 0;
+}
+
+int opty_hip_output_invalidate(opty_hip_problem *p, double *jac) {
+    if (!p) return fail("null handle");
+    if (!jac) {
+        p->invalidate_outputs();
+        return 0;
+    }
+    RegisteredOutput *o = find_output(p, jac);
+    if (!o) return fail("output %p is not registered", (void *)jac);
+    o->valid = false;
+    return 0;
+}
+
 int opty_hip_routing(opty_hip_problem *p, int64_t node_count,
                      int32_t *calibrated, int32_t *fused_loses,
                      int32_t *jac_via_fused, float *ms3) {
     if (!p) return fail("null handle");
     if (node_count < 0) return fail("negative node count");
     const long long nblk = (node_count + 63)/64;
+    bool var = false;
+    for (const auto &sv : p->served)
+        if (sv.first == nblk) var = sv.second;
     const Route *hit = nullptr;
     for (const Route &r : p->routes)
-        if (r.nblk == nblk) hit = &r;
+        if (r.nblk == nblk && r.var == var) hit = &r;
     const int banned = p->d.routing & (OPTY_HIP_ROUTE_NO_JAC_KERNEL |
                                        OPTY_HIP_ROUTE_NO_FUSED_KERNEL);
     bool fl = hit ? hit->fused_loses : p->d.fused_loses != 0;
     bool jv = hit ? hit->jac_via_fused : p->d.jac_via_fused != 0;
     if (banned & OPTY_HIP_ROUTE_NO_JAC_KERNEL) { fl = false; jv = true; }
     if (banned & OPTY_HIP_ROUTE_NO_FUSED_KERNEL) { fl = true; jv = false; }
-    if (calibrated) *calibrated = hit ? 1 : 0;
+    if (calibrated) *calibrated = (hit ? 1 : 0) | (var ? 2 : 0);
     if (fused_loses) *fused_loses = fl;
     if (jac_via_fused) *jac_via_fused = jv && !fl;
     if (ms3) {

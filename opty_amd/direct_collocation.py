@@ -939,7 +939,44 @@ class ConstraintCollocator(object):
         self._specialized_for = (par, h)
         return self._literal_values
 
+    #: kernels of the restricted flavour (``emit_hip.emit_module``)
+    _RESTRICTED_KERNELS = ('opty_jac_var', 'opty_conjac_var')
+
     def _build_code_object(self, opt_level=None):
+        """:meth:`_build_checked`'s code object, with the verdict on its
+        restricted kernels (``opty_jac_var`` / ``opty_conjac_var``: what
+        evaluations into a registered output launch) in
+        ``meta['restricted_ok']``.  They are an extra: a build in which one
+        of them spills vector registers, carries the EXEC-copy pattern of
+        the static ISA check, or sits next to a banned full kernel is used
+        WITHOUT them (the descriptor says the module has none, registered
+        outputs are written whole) -- never rebuilt for their sake."""
+        from . import isa_check
+        hsaco, meta = self._build_checked(opt_level)
+        if 'jac_var' not in meta['kernels']:
+            return hsaco, meta
+        why = None
+        if meta.get('banned_kernels'):
+            why = 'full kernels banned: %s' % (meta['banned_kernels'],)
+        else:
+            spills = hb.vgpr_spills(hsaco, self._RESTRICTED_KERNELS)
+            if spills:
+                why = 'vector spills: %s' % (spills,)
+            else:
+                try:
+                    hits = isa_check.exec_copies(
+                        hsaco, list(self._RESTRICTED_KERNELS))
+                except (OSError, subprocess.SubprocessError) as err:
+                    hits = {'isa_check': str(err)}
+                if hits:
+                    why = 'static ISA check: %s' % (dict(hits),)
+        if why:
+            logger.info('the restricted kernels of %s are not used (%s)',
+                        os.path.basename(hsaco), why)
+        return hsaco, dict(meta, restricted_ok=why is None,
+                           restricted_refused=why)
+
+    def _build_checked(self, opt_level=None):
         """The code object this collocator uses: :meth:`_build_spill_free`'s,
         unless the static ISA check (``opty_amd.isa_check``: a vector
         register copied into an accumulation register under a narrowed EXEC
@@ -1442,15 +1479,29 @@ class ConstraintCollocator(object):
             # reads a register it never wrote may come out right with ONE
             # pattern (the wrong-value counts of the frozen builds follow
             # the pattern: profiles/r05_poison_probe.txt)
+            restricted = bool(self._restricted_geometry(meta)[
+                'var_jac_wgs_per_block'])
             for pattern in hb.POISONS:
-                con, jac, con2, jac2 = self._evaluate_build(
-                    meta, hsaco, seed=seed, span=span, pattern=pattern)
+                con, jac, con2, jac2, *var = self._evaluate_build(
+                    meta, hsaco, seed=seed, span=span, pattern=pattern,
+                    restricted=restricted)
                 got = {
                     'opty_con': self._row_error(con, rcon, con_row, fcon),
                     'opty_jac': self._row_error(jac, rjac, jac_row, fjac),
                     'opty_conjac': max(
                         self._row_error(con2, rcon, con_row, fcon),
                         self._row_error(jac2, rjac, jac_row, fjac))}
+                if restricted:
+                    # the restricted kernels, each into a registered buffer
+                    # that the full kernel filled for ANOTHER free vector:
+                    # compared whole, so a line they must write and do not
+                    # shows as the other vector's value
+                    jac3, con4, jac4 = var
+                    got['opty_jac_var'] = self._row_error(jac3, rjac,
+                                                          jac_row, fjac)
+                    got['opty_conjac_var'] = max(
+                        self._row_error(con4, rcon, con_row, fcon),
+                        self._row_error(jac4, rjac, jac_row, fjac))
                 worst = {k: max(v, worst.get(k, 0.0))
                          for k, v in got.items()}
             return worst
@@ -1663,7 +1714,7 @@ class ConstraintCollocator(object):
                     np.nan_to_num(jac*unit, nan=0.0, posinf=0.0))
 
     def _evaluate_build(self, meta, hsaco, seed=7, span=(-1.0, 1.0),
-                        pattern=None):
+                        pattern=None, restricted=False):
         """``[con, jac, fused con, fused jac]`` of one code object of this
         problem's module on the first ``_VERIFY_NODES`` nodes: separate and
         fused launches, host buffers, no instance tails (scalar code)."""
@@ -1719,10 +1770,36 @@ class ConstraintCollocator(object):
             hb.poison_registers(pattern)
             h.eval_con_jac(dfree, outs[2], outs[3], hb.DEVICE)
             h.synchronize()
-            con, jac, con2, jac2 = [o.numpy() for o in outs]
+            if restricted:
+                # ``[..., jac (opty_jac_var), con, jac (opty_conjac_var)]``
+                # as well: registered outputs, written whole for another
+                # seed's free vector first, then by the restricted kernels
+                other = hb.DeviceVector(
+                    self._verification_inputs(seed + 1000, span)[1],
+                    self._device)
+                outs += [hb.DeviceVector(np.full(n, np.nan), self._device)
+                         for n in (nnz, ncon, nnz)]
+                for jac in (outs[4], outs[6]):
+                    h.output_register(jac)
+                h.eval_jac(other, outs[4], hb.DEVICE)
+                h.eval_con_jac(other, outs[5], outs[6], hb.DEVICE)
+                h.synchronize()
+                hb.poison_registers(pattern)
+                h.eval_jac(dfree, outs[4], hb.DEVICE)
+                h.synchronize()
+                if h.routing()['flavour'] != 'restricted' and os.environ.get(
+                        'OPTY_HIP_DENSE_OUTPUT', '0') in ('', '0'):
+                    raise hb.HipBackendError(
+                        'the restricted Jacobian kernel did not serve a '
+                        'registered output')
+                hb.poison_registers(pattern)
+                h.eval_con_jac(dfree, outs[5], outs[6], hb.DEVICE)
+                h.synchronize()
+                other.close()
+            vals = [o.numpy() for o in outs]
             for o in outs + [dfree]:
                 o.close()
-            return [con, jac, con2, jac2]
+            return vals
         finally:
             h.close()
 
@@ -1889,7 +1966,21 @@ class ConstraintCollocator(object):
             jac_persist=meta['kernels']['jac'].get('persist', 0),
             fused_persist=meta['kernels']['conjac'].get('persist', 0),
             jac_class_cost=self._class_cost(meta, 'jac'),
-            fused_class_cost=self._class_cost(meta, 'conjac'))
+            fused_class_cost=self._class_cost(meta, 'conjac'),
+            **self._restricted_geometry(meta))
+
+    def _restricted_geometry(self, meta):
+        """``opty_hip_desc.var_*``: zeros unless the module carries the
+        restricted kernels and the build accepted them."""
+        ok = meta.get('restricted_ok') is True and \
+            self._jacobian_layout == 'coo'
+        jv, fv = (meta['kernels'][k] for k in ('jac_var', 'conjac_var')) \
+            if ok else ({}, {})
+        return dict(
+            var_jac_wgs_per_block=jv.get('wgs_per_block', 0),
+            var_jac_waves_per_wg=jv.get('waves_per_wg', 0),
+            var_fused_wgs_per_block=fv.get('wgs_per_block', 0),
+            var_fused_waves_per_wg=fv.get('waves_per_wg', 0))
 
     def _routing_bits(self, meta):
         """``opty_hip_desc.routing``: the handle calibrates which kernels
@@ -1975,7 +2066,27 @@ class ConstraintCollocator(object):
         self._install_tables(hip)
         self._kernel_meta = meta
         self._hip = hip
+        for jac, a, b in getattr(self, '_owned_outputs', ()):
+            hip.output_register(jac, a, b)
         return hip
+
+    def _register_output(self, jac, node_begin, node_end):
+        """``HipProblem.output_register`` for a device Jacobian buffer the
+        caller owns for this collocator's lifetime -- now, or as soon as
+        the handle exists (it is built lazily)."""
+        if not hasattr(self, '_owned_outputs'):
+            self._owned_outputs = []
+        self._owned_outputs.append((jac, node_begin, node_end))
+        if self._hip is not None:
+            self._hip.output_register(jac, node_begin, node_end)
+
+    def _unregister_output(self, jac):
+        owned = getattr(self, '_owned_outputs', [])
+        keep = [o for o in owned if o[0] is not jac]
+        if len(keep) != len(owned):
+            self._owned_outputs = keep
+            if self._hip is not None and getattr(self._hip, '_h', None):
+                self._hip.output_unregister(jac)
 
     def _respecialize(self, hip):
         self._literal_values = None

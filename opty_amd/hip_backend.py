@@ -29,7 +29,7 @@ DEFAULT_CACHE = os.path.join(_PKG, '_cache')
 ARCH = 'gfx950'
 
 #: OPTY_HIP_ABI_VERSION of include/opty_hip.h these bindings were written for
-ABI_VERSION = 7
+ABI_VERSION = 8
 HOST, DEVICE = 0, 1
 #: hipStreamLegacy: the null / legacy default stream (torch's default)
 STREAM_LEGACY = 1
@@ -340,7 +340,10 @@ class _Desc(ctypes.Structure):
             'con_waves_per_wg', 'layout', 'inst_folded', 'fused_loses',
             'jac_via_fused', 'jac_persist', 'fused_persist', 'routing')] + [
         ('jac_class_cost', ctypes.c_float*32),
-        ('fused_class_cost', ctypes.c_float*32)]
+        ('fused_class_cost', ctypes.c_float*32)] + [
+        (name, ctypes.c_int32) for name in (
+            'var_jac_wgs_per_block', 'var_jac_waves_per_wg',
+            'var_fused_wgs_per_block', 'var_fused_waves_per_wg')]
 
     def __init__(self, **kw):
         for key in ('jac_class_cost', 'fused_class_cost'):
@@ -501,6 +504,10 @@ _SIGNATURES = {
     'opty_hip_hessian_nnz': (ctypes.c_int64, [_P]),
     'opty_hip_eval_hess': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_hessian_indices': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32]),
+    'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
+                                                ctypes.c_int64]),
+    'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
+    'opty_hip_output_invalidate': (ctypes.c_int, [_P, _P]),
     'opty_hip_abi_version': (ctypes.c_int, []),
     'opty_hip_device_count': (ctypes.c_int, []),
     'opty_hip_last_error': (ctypes.c_char_p, []),
@@ -769,6 +776,9 @@ class HipProblem(object):
         self.desc = dict(desc)
         if getattr(self, '_stream_ptr', None):
             self.set_stream(self._stream_ptr)
+        # the owners' word holds for the object, not for the C handle
+        for ptr, (a, b) in list(getattr(self, '_outputs', {}).items()):
+            _check(self._lib.opty_hip_output_register(self._h, ptr, a, b))
 
     # -- configuration -------------------------------------------------------
     def set_stream(self, stream_ptr):
@@ -919,6 +929,31 @@ class HipProblem(object):
             self._h, what, _ptr(free), _ptr(con), con_stride, _ptr(jac),
             node_begin, node_end))
 
+    def output_register(self, jac, node_begin=0, node_end=None):
+        """``opty_hip_output_register``: the caller OWNS the device buffer
+        ``jac`` (tensor or address), passes it for the constraint nodes
+        ``[node_begin, node_end)`` (default: all) and nobody else writes to
+        it between two evaluations -- which may then leave the
+        node-invariant entries as the previous evaluation wrote them.  Kept
+        across :meth:`reload`.  Unregister before the memory is released."""
+        if node_end is None:
+            node_end = self.desc['N'] - 1
+        _check(self._lib.opty_hip_output_register(
+            self._h, _ptr(jac), int(node_begin), int(node_end)))
+        if not hasattr(self, '_outputs'):
+            self._outputs = {}
+        self._outputs[_ptr(jac)] = (int(node_begin), int(node_end))
+
+    def output_unregister(self, jac):
+        """``opty_hip_output_unregister``."""
+        _check(self._lib.opty_hip_output_unregister(self._h, _ptr(jac)))
+        getattr(self, '_outputs', {}).pop(_ptr(jac), None)
+
+    def output_invalidate(self, jac=None):
+        """``opty_hip_output_invalidate``: the next evaluation into the
+        registered buffer ``jac`` (None: into any) writes everything."""
+        _check(self._lib.opty_hip_output_invalidate(self._h, _ptr(jac)))
+
     def eval_instance(self, free, con_tail, jac_tail):
         """The instance-constraint values / partials from the global device
         ``free`` into device buffers (either may be None); see
@@ -940,7 +975,11 @@ class HipProblem(object):
         with ``routing`` ('calibrated' once the handle has measured that
         launch size on its device, else 'plan'), ``fused_loses``,
         ``jac_via_fused`` and, when calibrated, the measured ``ms`` of
-        ``opty_conjac`` / ``opty_con`` / ``opty_jac``."""
+        ``opty_conjac`` / ``opty_con`` / ``opty_jac``; ``flavour`` is
+        ``'restricted'`` when the last Jacobian launch of that size was
+        served by ``opty_conjac_var`` / ``opty_jac_var`` (a registered
+        output, :meth:`output_register`: flags and times are then those
+        kernels'), else ``'full'``."""
         if nodes is None:
             nodes = self.desc['N'] - 1
         cal, fl, jv = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
@@ -950,10 +989,12 @@ class HipProblem(object):
             ctypes.byref(jv), ms))
         banned = self.desc.get('routing', 0) & (ROUTE_NO_JAC_KERNEL |
                                                 ROUTE_NO_FUSED_KERNEL)
+        restricted, cal.value = bool(cal.value & 2), cal.value & 1
         out = dict(routing='calibrated' if cal.value else (
                        'fixed: a spilling kernel is banned' if banned
                        else 'plan'),
-                   fused_loses=bool(fl.value), jac_via_fused=bool(jv.value))
+                   fused_loses=bool(fl.value), jac_via_fused=bool(jv.value),
+                   flavour='restricted' if restricted else 'full')
         if cal.value:
             out['ms'] = dict(opty_conjac=ms[0], opty_con=ms[1], opty_jac=ms[2])
         return out

@@ -368,6 +368,13 @@ class ShardedCollocator(object):
         f64 = dict(dtype=torch.float64, device=self.device)
         self.con_local = torch.empty((self.M, cnt), **f64)
         self.jac_local = torch.empty(cnt*self.P, **f64)
+        if self._hip_mode and cnt > 0:
+            # this tensor is the collocator's for its lifetime and only the
+            # kernels write to it: evaluations after the first leave its
+            # node-invariant entries alone (opty_hip_output_register; the
+            # handle is built lazily and may be replaced -- the collocator
+            # registers the buffer with every handle it makes)
+            col._register_output(self.jac_local, self.a, self.b)
         self.inst_con = torch.empty(self.o, **f64)
         self.inst_jac = torch.empty(self.nnz_inst, **f64)
         self._global = None         # (con, jac) on ranks that receive
@@ -375,6 +382,19 @@ class ShardedCollocator(object):
         self._in_place = False
         self._stream = None
         self._last_free = None
+
+    def close(self):
+        """Takes back the registration of :attr:`jac_local` with the HIP
+        handle (before the tensor's memory can be used for something
+        else)."""
+        if getattr(self, '_hip_mode', False) and \
+                getattr(self, 'jac_local', None) is not None:
+            try:
+                self.collocator._unregister_output(self.jac_local)
+            except Exception:       # interpreter shutdown: handle gone
+                pass
+
+    __del__ = close
 
     # -- layout ---------------------------------------------------------------
     @property
@@ -526,7 +546,16 @@ class ShardedCollocator(object):
         does, so that its own share is never copied).  ``sync=False`` skips
         re-reading the known maps (the caller installed them,
         :meth:`set_known`).  The instance constraints are not part of a
-        shard: :meth:`evaluate_instance`, or the re-assembly calls."""
+        shard: :meth:`evaluate_instance`, or the re-assembly calls.
+
+        :attr:`jac_local` is READ-ONLY between calls (the contract of the
+        array ``generate_jacobian_function`` returns): it is registered with
+        the HIP handle as a persistent output, so after the first
+        evaluation only the lines of a block that hold an entry which can
+        change are written again; a caller that did write into it calls
+        ``collocator.hip.output_invalidate(jac_local)``.  The in-place views
+        into the gathered global vectors are not registered: they are
+        written whole every time."""
         if free.numel() != self._num_free():
             raise ValueError('free must have {} entries, got {}'.format(
                 self._num_free(), free.numel()))
