@@ -171,10 +171,11 @@ typedef struct opty_hip_desc {
 /* Version of this header's structs and signatures; opty_hip_abi_version()
  * returns the one the library was built from.  A client built against another
  * version must not call the library: the descriptor grew in 5, 6, 7 and 8
- * (8: the restricted kernels' geometry, opty_hip_output_*), and
+ * (8: the restricted kernels' geometry, opty_hip_output_*; 9: the
+ * opty_hip_jacprod_* entry points), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
-#define OPTY_HIP_ABI_VERSION 8
+#define OPTY_HIP_ABI_VERSION 9
 int opty_hip_abi_version(void);
 
 /* (The build verification's device side -- register poisoner, instruction
@@ -649,6 +650,46 @@ int opty_hip_eval_hess(opty_hip_hessian *h, const double *free,
 /* int64 row / column indices of every hess value, same order. */
 int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
                              int64_t *cols, int32_t mem);
+
+/* ---- matrix-free Jacobian products ------------------------------------------
+ * J is the matrix of opty_hip_jacobian_indices + opty_hip_eval_jac: shape
+ * (num_constraints, num_free), the SUM of its triplets; the products do not
+ * depend on the Jacobian's layout or pruning.
+ *   jvp : out = J(free) v,   v of num_free doubles, out of num_constraints
+ *         doubles ordered like `con` (j*(N-1) + i, then the o instance
+ *         constraints);
+ *   vjp : out = J(free)^T w, w of num_constraints doubles, out of num_free
+ *         doubles ordered like `free`.
+ * Nothing of the size of the matrix is read or written: a product reads
+ * `free` and one vector and writes one vector.  Every entry of `out` is
+ * written exactly once per call, in a fixed order of operations (no
+ * floating-point atomics): the same inputs give the same bits.
+ * The code object exports `opty_jvp` (grid.y = jvp_strips), `opty_jvp_inst`,
+ * `opty_vjp` (blocks of 64 lanes that advance by 63 constraint nodes; grid.y
+ * = vjp_strips) and `opty_vjp_fin`.
+ *
+ * A product handle BORROWS its problem handle exactly as a Hessian handle
+ * does, and must be destroyed before it. */
+typedef struct opty_hip_jacprod opty_hip_jacprod;
+
+typedef struct opty_hip_jacprod_desc {
+    int32_t jvp_strips; /* workgroups per 64-node block of opty_jvp            */
+    int32_t vjp_strips; /* workgroups per 63-node block of opty_vjp            */
+    int32_t num_tail;   /* r + s: tail entries of `free` (block partials)      */
+    int32_t nnz_inst;   /* first partials of the instance constraints          */
+} opty_hip_jacprod_desc;
+
+int opty_hip_jacprod_create(opty_hip_problem *p,
+                            const opty_hip_jacprod_desc *desc,
+                            const char *code_object_path,
+                            opty_hip_jacprod **out);
+int opty_hip_jacprod_destroy(opty_hip_jacprod *h);
+/* All three arrays in `mem` memory.  Synchronous for OPTY_HIP_HOST, enqueued
+ * on the problem's stream for OPTY_HIP_DEVICE. */
+int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free,
+                         const double *v, double *out, int32_t mem);
+int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free,
+                         const double *w, double *out, int32_t mem);
 
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);

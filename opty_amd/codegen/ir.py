@@ -44,7 +44,15 @@ UNARY = ('sqrt', 'sin', 'cos', 'tan', 'exp', 'log', 'abs', 'sign', 'asin',
 #: Lagrange multiplier of equation ``index`` at the constraint node,
 #: ``lagrange[index*(N-1) + i]`` (Hessian programs,
 #: ``program.build_hessian_program``): per node, so NOT node-invariant.
-INPUT_KINDS = ('cur', 'adj', 'par', 'h', 'free', 'lam')
+#: ``vcur``/``vadj``/``vpar``/``vh`` are the entries of a direction vector
+#: ``v`` (shaped like ``free``) that sit where ``cur``/``adj``/``par``/``h`` of
+#: the same index sit in ``free`` (Jacobian-product programs,
+#: ``program.build_jacobian_product_program``); ``dir`` is the pseudo-column a
+#: tangent sweep differentiates along, never reachable from a root.
+INPUT_KINDS = ('cur', 'adj', 'par', 'h', 'free', 'lam', 'vcur', 'vadj',
+               'vpar', 'vh', 'dir')
+#: kinds whose value is the same at every constraint node
+UNIFORM_KINDS = ('par', 'h', 'free', 'vpar', 'vh', 'dir')
 
 
 class DAG(object):
@@ -72,7 +80,7 @@ class DAG(object):
             if op == CONST:
                 self.uni.append(True)
             elif op == INPUT:
-                self.uni.append(args[0] in ('par', 'h', 'free'))
+                self.uni.append(args[0] in UNIFORM_KINDS)
             else:
                 self.uni.append(all(self.uni[j] for j in self.operands(i)))
         return i

@@ -282,7 +282,42 @@ class Lowerer(object):
         return d.pow(base, exp_node)
 
 
-def forward_jacobian(dag, outputs, wrt_inputs, chain=None):
+def _angle_pair(dag, i):
+    """Recognises the two angle-difference forms multibody equations arrive
+    in: ``cos x cos y + sin x sin y`` (= cos(x - y)) and ``sin x cos y - cos x
+    sin y`` (= sin(x - y)), ``x != y``.  Returns ``('cos' | 'sin', x, y)`` or
+    None."""
+    d = dag
+    op, (p, r) = d.op[i], d.args[i]
+    if d.op[p] != ir.MUL or d.op[r] != ir.MUL:
+        return None
+    fp = [(d.op[k], d.args[k][0]) for k in d.args[p]]
+    fr = [(d.op[k], d.args[k][0]) for k in d.args[r]]
+    if any(f[0] not in ('sin', 'cos') for f in fp + fr):
+        return None
+    if op == ir.ADD:
+        if fp[0][0] == 'sin':
+            fp, fr = fr, fp
+        if [f[0] for f in fp] != ['cos', 'cos'] or \
+                [f[0] for f in fr] != ['sin', 'sin']:
+            return None
+        x, y = fp[0][1], fp[1][1]
+        if x == y or {x, y} != {fr[0][1], fr[1][1]}:
+            return None
+        return 'cos', x, y
+    # SUB: p = sin x cos y, r = cos x sin y
+    sp = dict(fp)
+    sr = dict(fr)
+    if len(sp) != 2 or len(sr) != 2:
+        return None
+    x, y = sp['sin'], sp['cos']
+    if x == y or sr['cos'] != x or sr['sin'] != y:
+        return None
+    return 'sin', x, y
+
+
+def forward_jacobian(dag, outputs, wrt_inputs, chain=None,
+                     angle_pairs=False):
     """Sparse forward-mode Jacobian on the DAG.
 
     ``outputs``: node ids of the M expressions; ``wrt_inputs``: node ids (INPUT
@@ -290,6 +325,14 @@ def forward_jacobian(dag, outputs, wrt_inputs, chain=None):
     ``{input node: [(wrt input node, derivative node)]}`` for inputs that are
     themselves known functions of a differentiation variable.  Returns an
     ``M x C`` list of lists of node ids (``dag.zero`` for structural zeros).
+
+    ``angle_pairs``: differentiate ``cos x cos y + sin x sin y`` as ``-(sin x
+    cos y - cos x sin y) (dx - dy)`` and ``sin x cos y - cos x sin y`` as
+    ``(cos x cos y + sin x sin y) (dx - dy)`` -- the same derivative, three
+    operations per column in place of seven, and the factor is the other
+    form, which such equations hold already (mass-matrix and centripetal
+    terms of a chain of bodies).  Off by default: the Jacobian program's
+    entries keep the association they have.
     """
     chain = chain or {}
     d = dag
@@ -324,7 +367,19 @@ def forward_jacobian(dag, outputs, wrt_inputs, chain=None):
         else:
             a = d.args[i]
             ga = grad[a[0]] if op != ir.SELECT else None
-            if op == ir.ADD:
+            pair = _angle_pair(d, i) if angle_pairs and \
+                op in (ir.ADD, ir.SUB) else None
+            if pair is not None:
+                kind, x, y = pair
+                cx, cy = d.unary('cos', x), d.unary('cos', y)
+                sx, sy = d.unary('sin', x), d.unary('sin', y)
+                if kind == 'cos':       # d cos(x - y) = -sin(x - y) (dx - dy)
+                    f = d.sub(d.mul(cx, sy), d.mul(sx, cy))
+                else:                   # d sin(x - y) = cos(x - y) (dx - dy)
+                    f = d.add(d.mul(cx, cy), d.mul(sx, sy))
+                g = combine(scaled(grad[x], f) if grad[x] else {},
+                            scaled(grad[y], f) if grad[y] else {}, -1)
+            elif op == ir.ADD:
                 g = combine(ga, grad[a[1]])
             elif op == ir.SUB:
                 g = combine(ga, grad[a[1]], -1)

@@ -366,6 +366,192 @@ def build_hessian_program(discrete_eom, state_cur, state_adj, traj_cur,
         inst_hess_atoms=inst_atoms, num_inst_atoms=num_atoms)
 
 
+class JacobianProductProgram(CollocationProgram):
+    """Plain data of a Jacobian-product program
+    (:func:`build_jacobian_product_program`).
+
+    ``tan_out``: M node ids, the directional derivative of every defect
+    equation along ``v``; ``adj_out``: C node ids, ``d/d col_k sum_j lam_j
+    c_j``; ``adj_sides[k]``: :func:`column_side` of column ``k``;
+    ``inst_jac_out``: the instance constraints' first partials,
+    ``inst_pairs[t] = (k, a)`` the constraint and the atom (index into the
+    atom list) of partial ``t``."""
+
+    def row_columns(self):
+        """``[(row, lo, hi)]`` per ``free`` trajectory row: the adjoint
+        columns whose free index is ``row*N + i`` (``lo``) and ``row*N + i +
+        1`` (``hi``) at constraint node ``i``; None where the block has no
+        such column."""
+        rows = [[r, None, None] for r in range(self.n + self.q)]
+        for k, (row, off) in enumerate(self.adj_sides):
+            if row >= 0:
+                rows[row][1 + off] = k
+        return [tuple(r) for r in rows]
+
+    def tail_columns(self):
+        """``[(j, k)]``: adjoint column ``k`` is the tail entry ``(n+q)*N +
+        j`` of ``free`` (unknown parameter / free interval)."""
+        return sorted((off, k) for k, (row, off) in enumerate(self.adj_sides)
+                      if row < 0)
+
+
+def build_jacobian_product_program(discrete_eom, state_cur, state_adj,
+                                   traj_cur, traj_adj, num_known_traj,
+                                   parameters, num_known_par, h_sym,
+                                   variable_duration, wrt, method,
+                                   instance=None, implicit=()):
+    """Matrix-free products with the constraint Jacobian: arguments as
+    :func:`build_program`'s (same lowering, same ``wrt`` columns, same
+    implicit inputs).  Two sets of roots on one DAG:
+
+    * the TANGENT of every defect equation along a direction ``v`` shaped
+      like ``free``: ONE tangent is pushed through the DAG
+      (:func:`lower.forward_jacobian` with a single pseudo-column ``('dir',
+      0)`` whose seeds arrive through ``chain``: column ``k``'s seed is the
+      INPUT ``('vcur' | 'vadj' | 'vpar' | 'vh', index)`` with the kind and
+      index of the column's own input), so the cost is a small multiple of
+      the constraint evaluation's, not of the Jacobian's;
+    * the ADJOINT ``d/d col_k sum_j lam_j c_j`` over the per-node inputs
+      ``('lam', j)``, which carry ``w`` (the first half of
+      :func:`build_hessian_program`).
+
+    Both sweeps use the angle-difference rule of
+    :func:`lower.forward_jacobian` (``angle_pairs``): the mass-matrix and
+    centripetal factors of a chain of bodies are differentiated in three
+    operations instead of seven.
+
+    Implicit known trajectories stay supported (only ``dr/dx`` is needed):
+    the tangent of ``r_i`` is ``dr_i v_x``, the adjoint goes through the
+    same ``chain`` as :func:`build_program`'s.  The instance constraints
+    contribute their first partials as in the Jacobian program."""
+    dag = ir.DAG()
+    n = len(state_cur)
+    m = len(traj_cur)
+    q = m - num_known_traj
+    r = len(parameters) - num_known_par
+    table = {}
+    for k, s in enumerate(state_cur):
+        table[s] = dag.input('cur', k)
+    for k, s in enumerate(state_adj):
+        table[s] = dag.input('adj', k)
+    for k, s in enumerate(traj_cur):
+        table[s] = dag.input('cur', n + k)
+    if method == 'midpoint':
+        for k, s in enumerate(traj_adj):
+            table[s] = dag.input('adj', n + k)
+    for k, s in enumerate(parameters):
+        table[s] = dag.input('par', k)
+    table[h_sym] = dag.input('h', 0)
+
+    low = Lowerer(dag, table)
+    con_out = [low.lower(e) for e in discrete_eom]
+    collect = os.environ.get('OPTY_COLLECT', '1') != '0'
+    if collect:
+        # the compact form FIRST: both sweeps then differentiate one
+        # multiplication per collected term, not one per expanded term
+        con_out = collect_coefficients(dag, con_out)
+    wrt_nodes = [table[s] for s in wrt]
+    C = len(wrt)
+
+    chain = {}
+    seed = dag.input('dir', 0)
+    tchain = {}
+    for node in wrt_nodes:
+        kind, idx = dag.args[node]
+        tchain[node] = [(seed, dag.input('v' + kind, idx))]
+    for k, st, kd in implicit:
+        sides = ['cur'] + (['adj'] if method == 'midpoint' else [])
+        for side in sides:
+            link = dag.input(side, n + k)
+            dr = dag.input(side, n + kd)
+            chain[link] = [(dag.input(side, st), dr)]
+            tchain[link] = [(seed, dag.mul(dr, dag.input('v' + side, st)))]
+    tan = [row[0] for row in forward_jacobian(dag, con_out, [seed], tchain,
+                                              angle_pairs=True)]
+    lag = dag.sum([dag.mul(dag.input('lam', j), c)
+                   for j, c in enumerate(con_out)])
+    adj = forward_jacobian(dag, [lag], wrt_nodes, chain,
+                           angle_pairs=True)[0]
+    if collect:
+        # ... and once more over each kernel's own roots (the two sets never
+        # meet in one kernel); kept where it pays: re-collecting the
+        # derivative of an already collected sum can also undo sharing
+        def cost(roots):
+            return sum(dag.count_ops(roots).values())
+        tan = min(tan, collect_coefficients(dag, list(tan)), key=cost)
+        adj = min(adj, collect_coefficients(dag, list(adj)), key=cost)
+
+    rows = [('free', k) for k in range(n)]
+    rows += [('known', j) for j in range(num_known_traj)]
+    rows += [('free', n + j) for j in range(q)]
+    pars = [('known', k) for k in range(num_known_par)]
+    pars += [('tail', j) for j in range(r)]
+    h = ('tail', r) if variable_duration else ('fixed',)
+
+    inst_jac_out, inst_pairs, num_atoms, num_inst = [], [], 0, 0
+    if instance is not None:
+        exprs, atom_syms, grads = instance
+        itable = {s: dag.input('free', a) for a, s in enumerate(atom_syms)}
+        for k, s in enumerate(parameters[:num_known_par]):
+            itable[s] = dag.input('par', k)
+        ilow = Lowerer(dag, itable)
+        num_atoms = len(atom_syms)
+        num_inst = len(exprs)
+        pos = {s: a for a, s in enumerate(atom_syms)}
+        for k, (e, atoms) in enumerate(zip(exprs, grads)):
+            if not atoms:
+                continue
+            node = ilow.lower(e)
+            g = forward_jacobian(dag, [node], [itable[s] for s in atoms])[0]
+            inst_jac_out += g
+            inst_pairs += [(k, pos[s]) for s in atoms]
+
+    return JacobianProductProgram(
+        dag=dag, tan_out=tan, adj_out=adj, con_out=con_out, jac_out=[],
+        adj_sides=[column_side(n, q, method, k) for k in range(C)],
+        n=n, m=m, q=q, r=r, s=int(variable_duration), M=len(con_out), C=C,
+        num_known_traj=num_known_traj, num_known_par=num_known_par,
+        rows=rows, pars=pars, h=h, method=method,
+        cur_offset=1 if method == 'backward euler' else 0,
+        adj_offset=0 if method == 'backward euler' else 1,
+        inst_jac_out=inst_jac_out, inst_pairs=inst_pairs,
+        num_inst=num_inst, num_inst_atoms=num_atoms)
+
+
+def assemble_jvp(prog, N, tan, inst, v, atom_free_index):
+    """``J v`` from the values of a product program's roots: ``tan`` the M
+    tangent roots at the N-1 constraint nodes (scalars broadcast), ``inst``
+    the instance partials; in the order of ``constraints(free)``.  The host
+    counterpart of ``opty_jvp`` / ``opty_jvp_inst`` (tests, verification)."""
+    import numpy as np
+    ncn = N - 1
+    out = np.zeros(prog.M*ncn + prog.num_inst)
+    for j in range(prog.M):
+        out[j*ncn:(j + 1)*ncn] = tan[j]
+    for t, (k, a) in enumerate(prog.inst_pairs):
+        out[prog.M*ncn + k] += inst[t]*v[atom_free_index[a]]
+    return out
+
+
+def assemble_vjp(prog, N, adj, inst, w, atom_free_index):
+    """``J^T w`` from the values of a product program's roots: ``adj`` the C
+    adjoint roots at the N-1 constraint nodes; ordered like ``free``.  The
+    host counterpart of ``opty_vjp`` / ``opty_vjp_fin``."""
+    import numpy as np
+    ncn = N - 1
+    tail = (prog.n + prog.q)*N
+    out = np.zeros(tail + prog.r + prog.s)
+    for k, (row, off) in enumerate(prog.adj_sides):
+        val = np.broadcast_to(np.asarray(adj[k], dtype=float), (ncn,))
+        if row >= 0:
+            out[row*N + off:row*N + off + ncn] += val
+        else:
+            out[tail + off] += val.sum()
+    for t, (k, a) in enumerate(prog.inst_pairs):
+        out[atom_free_index[a]] += inst[t]*w[prog.M*ncn + k]
+    return out
+
+
 def matrix_program(dag, outputs, num_vec, num_const, shape):
     """Program of a plain matrix of expressions (the reference's
     ``ufuncify_matrix`` call shape, ``opty/utils.py:639-640``): ``outputs`` are

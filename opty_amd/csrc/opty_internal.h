@@ -9,6 +9,8 @@
 //                     device, chunked DMA, the scatter pool of host threads
 //                     and its NUMA placement, the segmented layout
 //   comm.cpp          RCCL communicator, broadcast of `free`, gather-v
+//   hessian.cpp       the Hessian handle (borrows a problem handle)
+//   jacprod.cpp       the Jacobian-product handle (J v, J^T w; borrows too)
 //   referee.cpp       (libopty_hip_referee.so) instruction-tape kernel and
 //                     register poisoner of the build verification
 #pragma once

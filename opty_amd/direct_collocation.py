@@ -26,6 +26,7 @@ import sympy.physics.mechanics as me
 
 from .utils import parse_free, sort_sympy
 from .codegen.program import build_program, build_hessian_program, \
+    build_jacobian_product_program, \
     varying_copies
 from .codegen.emit_hip import emit_module, EmitOptions
 from . import hip_backend as hb
@@ -859,6 +860,400 @@ class ConstraintCollocator(object):
         return hessian_indices(self._build_hessian_program(),
                                self.num_collocation_nodes,
                                [idx[f] for f in self._inst_atoms])
+
+    # ------------------------------------------------------------------
+    # matrix-free Jacobian products
+    # ------------------------------------------------------------------
+    def _build_jacprod_program(self):
+        """The Jacobian-product program
+        (:func:`opty_amd.codegen.program.build_jacobian_product_program`),
+        built on first use."""
+        if getattr(self, '_jacprod_program', None) is not None:
+            return self._jacprod_program
+        be = self.integration_method == 'backward euler'
+        instance = None
+        if self.instance_constraints is not None:
+            place = {f: sm.Symbol('opty_atom_%d' % a, real=True)
+                     for a, f in enumerate(self._inst_atoms)}
+            exprs = [sm.sympify(c).xreplace(place)
+                     for c in self.instance_constraints]
+            grads = [[place[f] for f in atoms]
+                     for atoms in self._inst_atoms_per_constraint]
+            instance = (exprs, [place[f] for f in self._inst_atoms], grads)
+        logger.info('Lowering the tangent and the adjoint of the constraint '
+                    'function.')
+        self._jacprod_program = build_jacobian_product_program(
+            list(self.discrete_eom),
+            self.current_discrete_state_symbols,
+            self.previous_discrete_state_symbols if be
+            else self.next_discrete_state_symbols,
+            self.current_discrete_specified_symbols,
+            self.next_discrete_specified_symbols,
+            self.num_known_input_trajectories,
+            self.parameters, self.num_known_parameters,
+            self.time_interval_symbol, self._variable_duration,
+            self._wrt(), self.integration_method, instance,
+            implicit=self._implicit_chain())
+        return self._jacprod_program
+
+    def _atom_free_index(self):
+        idx = self.instance_constraints_free_index_map \
+            if self.num_instance_constraints else {}
+        return [idx[f] for f in self._inst_atoms] if idx else []
+
+    def _jacprod_inputs(self, free, vec, nodes, what):
+        """``inputs(kind, index)`` of the product DAG at the constraint nodes
+        ``nodes`` (an index array): ``what`` = ``'jvp'`` -- ``vec`` is the
+        direction ``v`` -- or ``'vjp'`` -- ``vec`` is ``w``."""
+        prog = self._build_jacprod_program()
+        N = self.num_collocation_nodes
+        ncn = N - 1
+        base = self._hessian_like_inputs(prog, free, nodes)
+        vtail = vec[(prog.n + prog.q)*N:] if what == 'jvp' else None
+
+        def inputs(kind, k):
+            if kind in ('vcur', 'vadj'):
+                src, r = prog.rows[k]
+                assert src == 'free', (kind, k)
+                off = prog.cur_offset if kind == 'vcur' else prog.adj_offset
+                return vec[r*N:(r + 1)*N][nodes + off]
+            if kind == 'vpar':
+                return vtail[prog.pars[k][1]]
+            if kind == 'vh':
+                return vtail[prog.h[1]]
+            if kind == 'lam':
+                return vec[k*ncn + nodes]
+            return base(kind, k)
+        return inputs
+
+    def _hessian_like_inputs(self, prog, free, nodes):
+        """``inputs(kind, index)`` for the kinds every program shares
+        (``cur``, ``adj``, ``par``, ``h``, ``free``) at the nodes ``nodes``."""
+        N = self.num_collocation_nodes
+        n, q = prog.n, prog.q
+        tail = free[(n + q)*N:]
+        known = self._known_trajectory_array(free) \
+            if self.num_known_input_trajectories else None
+        kpar = [float(self.known_parameter_map[p])
+                for p in self.known_parameters]
+        idx = self.instance_constraints_free_index_map \
+            if self.num_instance_constraints else {}
+
+        def inputs(kind, k):
+            if kind in ('cur', 'adj'):
+                src, r = prog.rows[k]
+                row = free[r*N:(r + 1)*N] if src == 'free' else known[r]
+                off = prog.cur_offset if kind == 'cur' else prog.adj_offset
+                return row[nodes + off]
+            if kind == 'par':
+                src, r = prog.pars[k]
+                return kpar[r] if src == 'known' else tail[r]
+            if kind == 'h':
+                return self.node_time_interval if prog.h[0] == 'fixed' \
+                    else tail[prog.h[1]]
+            assert kind == 'free', kind
+            return free[idx[self._inst_atoms[k]]]
+        return inputs
+
+    #: operations per strip of ``opty_jvp`` / ``opty_vjp`` in the first
+    #: build; halved (then units made to recompute what they share) while a
+    #: build spills
+    _JACPROD_STRIP_OPS = 1500
+    _JACPROD_KERNELS = ('opty_jvp', 'opty_jvp_inst', 'opty_vjp',
+                        'opty_vjp_fin')
+
+    def _build_jacprod_code_object(self):
+        """``(hsaco, meta)`` of the product module: the first build whose
+        kernels spill no vector register (smaller strips, then units that
+        recompute what they share), through the static ISA check (a hit: the
+        uniform-sincos sibling is built in its place when it is clean).  A
+        module that spills whatever the cut is refused."""
+        from .codegen.emit_jacprod import emit_jacprod_module
+        from . import isa_check
+        prog = self._build_jacprod_program()
+        names = self._JACPROD_KERNELS
+        budget, forget = self._JACPROD_STRIP_OPS, False
+        tried = []
+        for _ in range(6):
+            source, cuts = emit_jacprod_module(prog, budget, forget)
+            hsaco = self._compile(source)
+            spills = hb.vgpr_spills(hsaco, names)
+            tried.append((budget, forget, spills))
+            if not spills:
+                break
+            if budget > 200:
+                budget //= 2
+            else:
+                forget = True
+        else:
+            raise hb.BuildRejected(
+                'every build of the Jacobian-product kernels spills vector '
+                'registers: %s' % tried, dict(tried=tried))
+        hits = isa_check.exec_copies(hsaco, names)
+        if hits:
+            src2, cuts2 = emit_jacprod_module(prog, budget, forget,
+                                              fast_trig=2)
+            twin = self._compile(src2)
+            if not hb.vgpr_spills(twin, names) and \
+                    not isa_check.exec_copies(twin, names):
+                hsaco, cuts, hits = twin, cuts2, {}
+        return hsaco, dict(jvp_strips=max(1, len(cuts[0])),
+                           vjp_strips=max(1, len(cuts[1])), strip_ops=budget,
+                           forget=forget, isa_exec_copies=hits)
+
+    #: constraint nodes the referee compares: the first two blocks of
+    #: ``opty_vjp`` (both sides of a block edge), the last two nodes and the
+    #: nodes of the instance atoms
+    _JACPROD_VERIFY_NODES = 128
+    #: nodes per tape run of the tail columns' sums (all nodes, in chunks)
+    _JACPROD_TAIL_CHUNK = 8192
+
+    def _verify_jacprod(self, handle):
+        """Holds a product build to its expression DAG before first use: both
+        products, on random ``free``, ``v`` and ``w`` in device buffers that
+        start as NaN, against the DAG as an instruction tape on the GPU
+        (``opty_hip_tape_run``) on a node window -- the tail columns of ``J^T
+        w`` on all nodes -- to 64 units of each entry's own rounding-error
+        bound.  Raises :class:`hip_backend.BuildRejected`."""
+        from .codegen.tape import Tape
+        from .codegen.errbound import evaluate_with_error_bound
+        prog = self._build_jacprod_program()
+        N = self.num_collocation_nodes
+        ncn, M = N - 1, prog.M
+        u = 2.0**-53
+        rng = np.random.default_rng(19)
+        free = rng.uniform(-1.0, 1.0, self.num_free)
+        if self._variable_duration:
+            free[-1] = 0.01
+        v = rng.uniform(-1.0, 1.0, self.num_free)
+        w = rng.uniform(-1.0, 1.0, self.num_constraints)
+        # (known trajectories given as functions of ``free``: those of THIS
+        # free vector; the next product installs its own again)
+        self._sync_known(self._hip, free)
+        vecs = [hb.DeviceVector(x, self._device) for x in (free, v, w)]
+        outs = [hb.DeviceVector(np.full(max(1, k), np.nan), self._device)
+                for k in (self.num_constraints, self.num_free)]
+        try:
+            handle.jvp(vecs[0], vecs[1], outs[0], hb.DEVICE)
+            handle.vjp(vecs[0], vecs[2], outs[1], hb.DEVICE)
+            self._hip.synchronize()
+            jv = outs[0].numpy()[:self.num_constraints]
+            jtw = outs[1].numpy()[:self.num_free]
+        finally:
+            for x in vecs + outs:
+                x.close()
+        atoms = self._atom_free_index()
+        extra = [ncn - 2, ncn - 1]
+        for f in atoms:
+            extra += [f % N - 1, f % N]
+        nodes = np.unique(np.clip(np.r_[
+            np.arange(min(ncn, self._JACPROD_VERIFY_NODES)),
+            np.array(extra, dtype=np.int64)], 0, ncn - 1))
+        worst = [0.0]
+
+        def check(what, have, want, bnd, mag):
+            err = np.abs(have - want)
+            tol = 64.0*u*bnd + 4.0*u*mag
+            if not np.all(err <= tol):
+                raise hb.BuildRejected(
+                    '%s disagrees with the instruction tape (max error %.3g)'
+                    % (what, np.nanmax(err)),
+                    dict(what=what, err=float(np.nanmax(err))))
+            if err.size:
+                worst[0] = max(worst[0], float(np.max(
+                    err/np.maximum(tol, 1e-300))))
+
+        def referee(roots, inputs, count):
+            """Tape values and error bounds of ``roots``, ``(len(roots),
+            count)`` each."""
+            if not roots:
+                return np.zeros((0, count)), np.zeros((0, count))
+            tape = Tape(prog.dag, roots)
+            vals = hb.tape_run(tape, tape.table(count, inputs), self._device)
+            _, bound = evaluate_with_error_bound(prog.dag, roots, inputs)
+            val = np.stack([vals[tape.slot[r]] for r in roots])
+            bnd = np.stack([np.broadcast_to(np.abs(np.asarray(
+                b, dtype=float)), (count,)) for b in bound])
+            return val, bnd
+
+        # J v: the defect rows, then the instance rows
+        fin = self._jacprod_inputs(free, v, nodes, 'jvp')
+        val, bnd = referee(list(prog.tan_out), fin, len(nodes))
+        for j in range(M):
+            check('jvp equation %d' % j, jv[j*ncn + nodes], val[j], bnd[j],
+                  np.abs(val[j]))
+        ival, ibnd = referee(list(prog.inst_jac_out), fin, 1)
+        ival, ibnd = ival[:, 0], ibnd[:, 0]
+        for k in range(prog.num_inst):
+            ts = [t for t, (kk, _) in enumerate(prog.inst_pairs) if kk == k]
+            vk = np.array([v[atoms[prog.inst_pairs[t][1]]] for t in ts])
+            terms = ival[ts]*vk
+            check('jvp instance row %d' % k, jv[M*ncn + k], terms.sum(),
+                  float((ibnd[ts]*np.abs(vk)).sum()),
+                  (len(ts) + 1)*float(np.abs(terms).sum()))
+
+        # J^T w: the trajectory rows on the window
+        rin = self._jacprod_inputs(free, w, nodes, 'vjp')
+        val, bnd = referee(list(prog.adj_out), rin, len(nodes))
+        want, wb, mag = (np.zeros(self.num_free) for _ in range(3))
+        seen = np.zeros(N + 1, dtype=bool)
+        seen[nodes] = True
+        pos = np.zeros(N + 1, dtype=np.int64)
+        pos[nodes] = np.arange(len(nodes))
+        p = np.arange(N)
+        checked = ((p == ncn) | seen[p]) & ((p == 0) | seen[p - 1])
+        has_lo, has_hi = checked & (p < ncn), checked & (p >= 1)
+        mask = np.zeros(self.num_free, dtype=bool)
+        for R, lo, hi in prog.row_columns():
+            row = slice(R*N, (R + 1)*N)
+            mask[row] = checked
+            for k, has, shift in ((lo, has_lo, 0), (hi, has_hi, 1)):
+                if k is None:
+                    continue
+                at = pos[p[has] - shift]
+                want[row][has] += val[k][at]
+                wb[row][has] += bnd[k][at]
+                mag[row][has] += np.abs(val[k][at])
+        for t, (k, a) in enumerate(prog.inst_pairs):
+            wk = w[M*ncn + k]
+            want[atoms[a]] += wk*ival[t]
+            wb[atoms[a]] += abs(wk)*ibnd[t]
+            mag[atoms[a]] += 2.0*abs(wk*ival[t])
+            assert mask[atoms[a]]
+        check('vjp trajectory rows', jtw[mask], want[mask], wb[mask],
+              mag[mask])
+
+        # ... and the tail columns: sums over ALL constraint nodes
+        tails = prog.tail_columns()
+        if tails:
+            roots = [prog.adj_out[k] for _, k in tails]
+            tot, tb, tm = (np.zeros(len(tails)) for _ in range(3))
+            for a in range(0, ncn, self._JACPROD_TAIL_CHUNK):
+                part = np.arange(a, min(ncn, a + self._JACPROD_TAIL_CHUNK))
+                val, bnd = referee(
+                    roots, self._jacprod_inputs(free, w, part, 'vjp'),
+                    len(part))
+                tot += val.sum(axis=1)
+                tb += bnd.sum(axis=1)
+                tm += np.abs(val).sum(axis=1)
+            tail0 = (prog.n + prog.q)*N
+            at = tail0 + np.array([j for j, _ in tails])
+            # a sum of ncn terms, whatever its order: ncn units of the sum
+            # of the magnitudes at the very most
+            check('vjp tail columns', jtw[at], tot, tb, 0.25*ncn*tm)
+        return dict(ok=True, referee='tape', nodes=len(nodes),
+                    tail_nodes=ncn if tails else 0,
+                    worst_fraction_of_tolerance=worst[0])
+
+    def _ensure_jacprod(self):
+        """The product handle (built, checked and verified on first use; it
+        borrows the problem handle's device data)."""
+        if getattr(self, '_jacprod', None) is not None:
+            return self._jacprod
+        hip = self._ensure_hip()
+        prog = self._build_jacprod_program()
+        hsaco, meta = self._build_jacprod_code_object()
+        handle = hb.HipJacobianProduct(hip, dict(
+            jvp_strips=meta['jvp_strips'], vjp_strips=meta['vjp_strips'],
+            num_tail=prog.r + prog.s, nnz_inst=len(prog.inst_jac_out)),
+            hsaco)
+        self._sync_known(hip, None)
+        try:
+            verdict = self._verify_jacprod(handle)
+        except hb.BuildRejected:
+            handle.release()
+            raise
+        self._jacprod_meta = dict(meta, hsaco=hsaco, verdict=verdict)
+        self._jacprod = handle
+        return handle
+
+    def _generate_product(self, which):
+        handle = self._ensure_jacprod()
+        hip = self._hip
+        nfree, ncon = self.num_free, self.num_constraints
+        nin, nout = (nfree, ncon) if which == 'jvp' else (ncon, nfree)
+        launch = handle.jvp if which == 'jvp' else handle.vjp
+        name = 'v' if which == 'jvp' else 'w'
+        result = hb.pinned_empty(nout)
+
+        def product(free, vec):
+            if hasattr(free, 'data_ptr'):
+                import torch
+                if tuple(free.shape) != (nfree,) or \
+                        tuple(vec.shape) != (nin,):
+                    raise ValueError('free / %s have the wrong shape' % name)
+                free = free.to(torch.float64).contiguous()
+                vec = vec.to(device=free.device,
+                             dtype=torch.float64).contiguous()
+                # (known trajectories given as functions of ``free`` are
+                # host callables: they alone need ``free`` on the host)
+                self._sync_known(hip, free.cpu().numpy()
+                                 if self._callable_known else None)
+                out = torch.empty(nout, dtype=torch.float64,
+                                  device=free.device)
+                torch.cuda.current_stream(free.device).synchronize()
+                launch(free, vec, out, hb.DEVICE)
+                hip.synchronize()
+                return out
+            free = self._host_free(free)
+            vec = np.ascontiguousarray(vec, dtype=np.float64)
+            if vec.shape != (nin,):
+                raise ValueError('{} must have shape ({},), got {}'.format(
+                    name, nin, vec.shape))
+            self._sync_known(hip, free)
+            launch(free, vec, result, hb.HOST)
+            return result
+        product.handle = handle
+        return product
+
+    def generate_jvp_function(self):
+        """Returns ``jvp(free, v) -> ndarray (num_constraints,)``: the
+        constraint Jacobian at ``free`` times ``v``, evaluated on the GPU
+        without forming the matrix; ordered like ``constraints(free)``.  The
+        matrix is the one of :meth:`jacobian_indices` and
+        ``generate_jacobian_function`` (the SUM of its triplets), whatever
+        ``prune_zeros`` and ``jacobian_layout`` are.  The result is a
+        persistent page-locked buffer that the next call overwrites.
+
+        ``free`` and ``v`` may also be torch CUDA tensors; the result is then
+        a new CUDA tensor (nothing crosses PCIe)."""
+        return self._generate_product('jvp')
+
+    def generate_vjp_function(self):
+        """Returns ``vjp(free, w) -> ndarray (num_free,)``: the transposed
+        constraint Jacobian at ``free`` times ``w`` (``w`` ordered like
+        ``constraints(free)``), ordered like ``free``; otherwise as
+        :meth:`generate_jvp_function`.  Bit-identical from call to call."""
+        return self._generate_product('vjp')
+
+    def jacobian_operator(self, free):
+        """The constraint Jacobian at ``free`` as a
+        ``scipy.sparse.linalg.LinearOperator`` of shape ``(num_constraints,
+        num_free)``: ``matvec`` / ``rmatvec`` are :meth:`generate_jvp_function`
+        / :meth:`generate_vjp_function` at that ``free`` (a copy is kept; a
+        torch CUDA tensor stays on the device).  Every product returns a new
+        array."""
+        from scipy.sparse.linalg import LinearOperator
+        if getattr(self, '_jacprod_functions', None) is None:
+            self._jacprod_functions = (self.generate_jvp_function(),
+                                       self.generate_vjp_function())
+        jvp, vjp = self._jacprod_functions
+        if hasattr(free, 'data_ptr'):
+            import torch
+            free = free.detach().clone()
+
+            def apply(f, x):
+                x = torch.from_numpy(np.ascontiguousarray(
+                    x, dtype=np.float64).reshape(-1)).to(free.device)
+                return f(free, x).cpu().numpy()
+        else:
+            free = self._host_free(free).copy()
+
+            def apply(f, x):
+                return np.array(f(free, np.asarray(x).reshape(-1)))
+        return LinearOperator(
+            (self.num_constraints, self.num_free), dtype=np.float64,
+            matvec=lambda x: apply(jvp, x), rmatvec=lambda x: apply(vjp, x))
 
     def generate_source(self):
         """HIP source of this problem's kernels and its launch metadata."""
@@ -2766,6 +3161,12 @@ class Problem(object):
     def jacobian(self, free):
         return self.con_jac(free)
 
+    def jacobian_operator(self, free):
+        """The constraint Jacobian at ``free`` as a matrix-free
+        ``scipy.sparse.linalg.LinearOperator``
+        (:meth:`ConstraintCollocator.jacobian_operator`)."""
+        return self.collocator.jacobian_operator(free)
+
     def intermediate(self, *args):
         self.obj_value.append(args[2])
 
@@ -2932,6 +3333,9 @@ class ShardedProblem(Problem):
             rows, cols = self.collocator.jacobian_indices()
         return (self.callbacks.constraints, self.callbacks.jacobian, rows,
                 cols)
+
+    def jacobian_operator(self, free):
+        raise NotImplementedError('Jacobian products are not sharded.')
 
     def serve(self):
         """Non-root ranks: evaluate on the root's command until shutdown."""

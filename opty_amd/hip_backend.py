@@ -29,7 +29,7 @@ DEFAULT_CACHE = os.path.join(_PKG, '_cache')
 ARCH = 'gfx950'
 
 #: OPTY_HIP_ABI_VERSION of include/opty_hip.h these bindings were written for
-ABI_VERSION = 8
+ABI_VERSION = 9
 HOST, DEVICE = 0, 1
 #: hipStreamLegacy: the null / legacy default stream (torch's default)
 STREAM_LEGACY = 1
@@ -75,7 +75,7 @@ def _hipcc():
 #: translation units of libopty_hip.so (csrc/opty_internal.h says what is
 #: where) and of the build referee's own library
 RUNTIME_SOURCES = ('runtime.cpp', 'programs.cpp', 'host_scatter.cpp',
-                   'comm.cpp', 'hessian.cpp')
+                   'comm.cpp', 'hessian.cpp', 'jacprod.cpp')
 REFEREE_SOURCES = ('referee.cpp',)
 REFEREE_PATH = os.path.join(_PKG, 'libopty_hip_referee.so')
 
@@ -396,6 +396,11 @@ class _HessDesc(ctypes.Structure):
                 ('inst_rows', ctypes.c_void_p), ('inst_cols', ctypes.c_void_p)]
 
 
+class _JacprodDesc(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'jvp_strips', 'vjp_strips', 'num_tail', 'nnz_inst')]
+
+
 class _ObjDesc(ctypes.Structure):
     _fields_ = [('N', ctypes.c_int64), ('n', ctypes.c_int32),
                 ('q', ctypes.c_int32), ('r', ctypes.c_int32),
@@ -504,6 +509,12 @@ _SIGNATURES = {
     'opty_hip_hessian_nnz': (ctypes.c_int64, [_P]),
     'opty_hip_eval_hess': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_hessian_indices': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32]),
+    'opty_hip_jacprod_create': (ctypes.c_int,
+                                [_P, ctypes.POINTER(_JacprodDesc),
+                                 ctypes.c_char_p, ctypes.POINTER(_P)]),
+    'opty_hip_jacprod_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_jacprod_jvp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    'opty_hip_jacprod_vjp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
                                                 ctypes.c_int64]),
     'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
@@ -1201,3 +1212,48 @@ class HipHessian(object):
     def indices(self, rows, cols, mem):
         _check(self._lib.opty_hip_hessian_indices(self._handle(), _ptr(rows),
                                                   _ptr(cols), mem))
+
+
+class HipJacobianProduct(object):
+    """One ``opty_hip_jacprod`` handle: ``J(free) v`` and ``J(free)^T w`` of a
+    :class:`HipProblem`, whose device data it borrows.  When the problem's C
+    handle is replaced (:meth:`HipProblem.reload`) or closed, this handle is
+    released first and created again for the new one on the next call."""
+
+    def __init__(self, problem, desc, hsaco_path):
+        self._lib = load_library()
+        self._problem = problem
+        self._desc = dict(desc)
+        self._hsaco = hsaco_path
+        self._h = None
+        import weakref
+        deps = problem.__dict__.setdefault('_dependents', weakref.WeakSet())
+        deps.add(self)
+        self._handle()
+
+    def _handle(self):
+        if self._h is None:
+            if not getattr(self._problem, '_h', None):
+                raise HipBackendError('the problem handle is closed')
+            d = _JacprodDesc(**self._desc)
+            h = _P()
+            _check(self._lib.opty_hip_jacprod_create(
+                self._problem._h, ctypes.byref(d), self._hsaco.encode(),
+                ctypes.byref(h)))
+            self._h = h
+        return self._h
+
+    def release(self):
+        if getattr(self, '_h', None):
+            self._lib.opty_hip_jacprod_destroy(self._h)
+            self._h = None
+
+    __del__ = release
+
+    def jvp(self, free, v, out, mem):
+        _check(self._lib.opty_hip_jacprod_jvp(self._handle(), _ptr(free),
+                                              _ptr(v), _ptr(out), mem))
+
+    def vjp(self, free, w, out, mem):
+        _check(self._lib.opty_hip_jacprod_vjp(self._handle(), _ptr(free),
+                                              _ptr(w), _ptr(out), mem))
