@@ -644,7 +644,11 @@ int opty_hip_hessian_destroy(opty_hip_hessian *h);
 int64_t opty_hip_hessian_nnz(const opty_hip_hessian *h);
 /* free: num_free doubles, lagrange: num_constraints doubles, hess:
  * hessian_nnz doubles, all in `mem` memory.  Synchronous for OPTY_HIP_HOST,
- * enqueued on the problem's stream for OPTY_HIP_DEVICE. */
+ * enqueued on the problem's stream for OPTY_HIP_DEVICE.
+ * OPTY_HIP_DEVICE with an even PH: `hess` must be 16-byte aligned (a node's
+ * entries are written with 16-byte stores); a pointer that is not is refused
+ * ("... must be 16-byte aligned ...") before anything is enqueued.  An odd PH
+ * and OPTY_HIP_HOST need no more than a double's alignment. */
 int opty_hip_eval_hess(opty_hip_hessian *h, const double *free,
                        const double *lagrange, double *hess, int32_t mem);
 /* int64 row / column indices of every hess value, same order. */

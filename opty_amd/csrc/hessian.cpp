@@ -10,6 +10,8 @@
 // instance constraints' entries after the node blocks).
 #include "opty_internal.h"
 
+#include <cstdint>
+
 using namespace opty;
 
 namespace {
@@ -109,6 +111,7 @@ int opty_hip_hessian_create(opty_hip_problem *p,
         (desc->nnz_inst > 0 &&
          hipModuleGetFunction(&h->k_inst, h->module, "opty_hess_inst") !=
              hipSuccess)) {
+        (void)hipGetLastError();    // not left behind for the caller's runtime
         (void)hipModuleUnload(h->module);
         delete h;
         return fail("opty_hess/opty_hess_inst missing from %s",
@@ -165,6 +168,12 @@ int opty_hip_eval_hess(opty_hip_hessian *h, const double *free_,
     if (!h || !free_ || !lagrange || !hess) return fail("null argument");
     if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
         return fail("bad memory kind %d", mem);
+    // an even PH is flushed with 16-byte stores at hess + (even offset)
+    // (opty_flush16): the caller's device pointer has to allow them
+    if (mem == OPTY_HIP_DEVICE && h->d.PH > 0 && h->d.PH % 2 == 0 &&
+        (reinterpret_cast<uintptr_t>(hess) & 15) != 0)
+        return fail("hess (%p) must be 16-byte aligned in device memory when "
+                    "PH (%d) is even", (void *)hess, h->d.PH);
     opty_hip_problem *p = h->p;
     if (int rc = use_device(p)) return rc;
     if (int rc = check_ready(p)) return rc;

@@ -6,8 +6,8 @@ finite difference of the GPU Jacobian and the ``Problem`` callbacks."""
 import numpy as np
 import pytest
 
-import dag_interp
 from golden_util import assert_close
+from hessian_cases import interpreted as _interpreted
 from test_hessian_cpu import _nonlinear_instance_pendulum
 
 from examples import problems
@@ -26,26 +26,6 @@ def _inputs(seed, col):
     if col._variable_duration:
         free[-1] = 0.02
     return free, rng.uniform(-1.0, 1.0, col.num_constraints)
-
-
-def _interpreted(col, free, lam, nodes=None):
-    """Values of the Hessian program from the CPU interpreter at the
-    constraint nodes ``nodes`` (all by default): ``(block (len(nodes), PH),
-    instance values, block bounds)``."""
-    prog = col._build_hessian_program()
-    ncn = col.num_collocation_nodes - 1
-    nodes = np.arange(ncn) if nodes is None else np.asarray(nodes)
-    inputs = col._hessian_inputs(free, lam, nodes)
-    vals, bound = dag_interp.evaluate_with_error_bound(
-        prog.dag, prog.hess_out, inputs)
-    block = np.stack([np.broadcast_to(np.asarray(v, dtype=float),
-                                      (len(nodes),)) for v in vals], axis=1)
-    bnd = np.stack([np.broadcast_to(np.asarray(v, dtype=float),
-                                    (len(nodes),)) for v in bound], axis=1)
-    ivals = dag_interp.evaluate(prog.dag, prog.inst_hess_out, inputs)
-    inst = np.array([float(v)*lam[prog.M*ncn + k]
-                     for v, k in zip(ivals, prog.inst_hess_con)])
-    return block, inst, bnd
 
 
 def _collocator(kw):
