@@ -64,6 +64,69 @@ class CollocationProgram(object):
         return len(self.jac_out)
 
 
+def _front_end(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
+               parameters, h_sym, method):
+    """``(dag, symbol table, con_out)`` every builder starts from: the DAG
+    inputs of the discrete symbols, in one fixed order (the node ids of an
+    emitted source depend on it), and the lowered defect equations."""
+    dag = ir.DAG()
+    n = len(state_cur)
+    table = {}
+    for k, s in enumerate(state_cur):
+        table[s] = dag.input('cur', k)
+    for k, s in enumerate(state_adj):
+        table[s] = dag.input('adj', k)
+    for k, s in enumerate(traj_cur):
+        table[s] = dag.input('cur', n + k)
+    if method == 'midpoint':
+        for k, s in enumerate(traj_adj):
+            table[s] = dag.input('adj', n + k)
+    for k, s in enumerate(parameters):
+        table[s] = dag.input('par', k)
+    table[h_sym] = dag.input('h', 0)
+    low = Lowerer(dag, table)
+    return dag, table, [low.lower(e) for e in discrete_eom]
+
+
+def _layout(state_cur, traj_cur, num_known_traj, parameters, num_known_par,
+            variable_duration, method):
+    """Keyword arguments of a :class:`CollocationProgram` that say where the
+    DAG inputs live in device memory (the same for every builder)."""
+    n, m = len(state_cur), len(traj_cur)
+    q = m - num_known_traj
+    r = len(parameters) - num_known_par
+    # row r of the slab: states then unknown inputs come from `free`
+    # (``free`` viewed as (n+q, N), opty/utils.py:308-318); known inputs from
+    # the known-trajectory buffer.  input_trajectories = known + unknown.
+    rows = [('free', k) for k in range(n)]
+    rows += [('known', j) for j in range(num_known_traj)]
+    rows += [('free', n + j) for j in range(q)]
+    pars = [('known', k) for k in range(num_known_par)]
+    pars += [('tail', j) for j in range(r)]
+    return dict(
+        n=n, m=m, q=q, r=r, s=int(variable_duration),
+        num_known_traj=num_known_traj, num_known_par=num_known_par,
+        rows=rows, pars=pars, method=method,
+        h=('tail', r) if variable_duration else ('fixed',),
+        cur_offset=1 if method == 'backward euler' else 0,
+        adj_offset=0 if method == 'backward euler' else 1)
+
+
+def _lower_instance(dag, exprs, atom_syms, grads, known_pars,
+                    skip_constants):
+    """Lowers the instance constraints into ``dag`` over the inputs ``('free',
+    a)`` of their atoms and the known parameters: yields ``(k, node of
+    expression k, nodes of its atoms)``.  ``skip_constants``: an expression
+    without atoms is not lowered at all."""
+    itable = {s: dag.input('free', a) for a, s in enumerate(atom_syms)}
+    for k, s in enumerate(known_pars):
+        itable[s] = dag.input('par', k)
+    ilow = Lowerer(dag, itable)
+    for k, (e, atoms) in enumerate(zip(exprs, grads)):
+        if atoms or not skip_constants:
+            yield k, ilow.lower(e), [itable[s] for s in atoms]
+
+
 def build_program(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
                   num_known_traj, parameters, num_known_par, h_sym,
                   variable_duration, wrt, method, instance=None,
@@ -92,25 +155,11 @@ def build_program(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
     instance constraints written over one placeholder Symbol per function
     atom; lowered into the same DAG with INPUT kind ``'free'``.
     """
-    dag = ir.DAG()
-    n = len(state_cur)
-    m = len(traj_cur)
-    q = m - num_known_traj
-    r = len(parameters) - num_known_par
-    table = {}
-    for k, s in enumerate(state_cur):
-        table[s] = dag.input('cur', k)
-    for k, s in enumerate(state_adj):
-        table[s] = dag.input('adj', k)
-    for k, s in enumerate(traj_cur):
-        table[s] = dag.input('cur', n + k)
-    if method == 'midpoint':
-        for k, s in enumerate(traj_adj):
-            table[s] = dag.input('adj', n + k)
-    for k, s in enumerate(parameters):
-        table[s] = dag.input('par', k)
-    table[h_sym] = dag.input('h', 0)
-
+    dag, table, con_out = _front_end(discrete_eom, state_cur, state_adj,
+                                     traj_cur, traj_adj, parameters, h_sym,
+                                     method)
+    n, q = len(state_cur), len(traj_cur) - num_known_traj
+    # (the links' inputs are all in the table already: no new node)
     chain = {}
     for k, st, kd in implicit:
         chain[dag.input('cur', n + k)] = [(dag.input('cur', st),
@@ -118,9 +167,6 @@ def build_program(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
         if method == 'midpoint':
             chain[dag.input('adj', n + k)] = [(dag.input('adj', st),
                                                dag.input('adj', n + kd))]
-
-    low = Lowerer(dag, table)
-    con_out = [low.lower(e) for e in discrete_eom]
     wrt_nodes = [table[s] for s in wrt]
     jac = forward_jacobian(dag, con_out, wrt_nodes, chain)
     con_out, jac = _collect(dag, con_out, jac)
@@ -146,41 +192,24 @@ def build_program(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
     for j in range(len(con_out)):
         row_start[j + 1] += row_start[j]
 
-    # row r of the slab: states then unknown inputs come from `free`
-    # (``free`` viewed as (n+q, N), opty/utils.py:308-318); known inputs from
-    # the known-trajectory buffer.  input_trajectories = known + unknown.
-    rows = [('free', k) for k in range(n)]
-    rows += [('known', j) for j in range(num_known_traj)]
-    rows += [('free', n + j) for j in range(q)]
-    pars = [('known', k) for k in range(num_known_par)]
-    pars += [('tail', j) for j in range(r)]
-    h = ('tail', r) if variable_duration else ('fixed',)
-
     inst_con_out, inst_jac_out, num_atoms = [], [], 0
     if instance is not None:
         exprs, atom_syms, grads = instance
-        itable = {s: dag.input('free', a) for a, s in enumerate(atom_syms)}
-        for k, s in enumerate(parameters[:num_known_par]):
-            itable[s] = dag.input('par', k)
-        ilow = Lowerer(dag, itable)
         num_atoms = len(atom_syms)
-        for e, atoms in zip(exprs, grads):
-            node = ilow.lower(e)
+        for _, node, nodes in _lower_instance(
+                dag, exprs, atom_syms, grads, parameters[:num_known_par],
+                skip_constants=False):
             inst_con_out.append(node)
-            if atoms:
-                g = forward_jacobian(dag, [node], [itable[s] for s in atoms])
-                inst_jac_out += g[0]
+            if nodes:
+                inst_jac_out += forward_jacobian(dag, [node], nodes)[0]
 
     return CollocationProgram(
-        dag=dag, con_out=con_out, jac_out=jac_out, n=n, m=m, q=q, r=r,
-        s=int(variable_duration), M=len(con_out), C=len(wrt),
-        num_known_traj=num_known_traj, num_known_par=num_known_par,
-        rows=rows, pars=pars, h=h, method=method,
-        cur_offset=1 if method == 'backward euler' else 0,
-        adj_offset=0 if method == 'backward euler' else 1,
-        inst_con_out=inst_con_out, inst_jac_out=inst_jac_out,
+        dag=dag, con_out=con_out, jac_out=jac_out, M=len(con_out),
+        C=len(wrt), inst_con_out=inst_con_out, inst_jac_out=inst_jac_out,
         num_inst_atoms=num_atoms, pattern=pattern,
-        pruned=bool(prune_zeros), layout=layout, row_start=row_start)
+        pruned=bool(prune_zeros), layout=layout, row_start=row_start,
+        **_layout(state_cur, traj_cur, num_known_traj, parameters,
+                  num_known_par, variable_duration, method))
 
 
 def column_side(n, q, method, k):
@@ -280,27 +309,10 @@ def build_hessian_program(discrete_eom, state_cur, state_adj, traj_cur,
             'the Hessian of a problem with implicit known trajectories (a '
             'known r(x(t)) with only dr/dx given) is not available: the '
             'second derivative of r is unknown.')
-    dag = ir.DAG()
-    n = len(state_cur)
-    m = len(traj_cur)
-    q = m - num_known_traj
-    r = len(parameters) - num_known_par
-    table = {}
-    for k, s in enumerate(state_cur):
-        table[s] = dag.input('cur', k)
-    for k, s in enumerate(state_adj):
-        table[s] = dag.input('adj', k)
-    for k, s in enumerate(traj_cur):
-        table[s] = dag.input('cur', n + k)
-    if method == 'midpoint':
-        for k, s in enumerate(traj_adj):
-            table[s] = dag.input('adj', n + k)
-    for k, s in enumerate(parameters):
-        table[s] = dag.input('par', k)
-    table[h_sym] = dag.input('h', 0)
-
-    low = Lowerer(dag, table)
-    con_out = [low.lower(e) for e in discrete_eom]
+    dag, table, con_out = _front_end(discrete_eom, state_cur, state_adj,
+                                     traj_cur, traj_adj, parameters, h_sym,
+                                     method)
+    n, q = len(state_cur), len(traj_cur) - num_known_traj
     lag = dag.sum([dag.mul(dag.input('lam', j), c)
                    for j, c in enumerate(con_out)])
     wrt_nodes = [table[s] for s in wrt]
@@ -318,27 +330,15 @@ def build_hessian_program(discrete_eom, state_cur, state_adj, traj_cur,
     pairs = [pairs[k] for k in kept]
     out = [out[k] for k in kept]
 
-    rows = [('free', k) for k in range(n)]
-    rows += [('known', j) for j in range(num_known_traj)]
-    rows += [('free', n + j) for j in range(q)]
-    pars = [('known', k) for k in range(num_known_par)]
-    pars += [('tail', j) for j in range(r)]
-    h = ('tail', r) if variable_duration else ('fixed',)
-
     inst_out, inst_con, inst_atoms, num_atoms = [], [], [], 0
     if instance is not None:
         exprs, atom_syms, grads, free_index = instance
-        itable = {s: dag.input('free', a) for a, s in enumerate(atom_syms)}
-        for k, s in enumerate(parameters[:num_known_par]):
-            itable[s] = dag.input('par', k)
-        ilow = Lowerer(dag, itable)
         num_atoms = len(atom_syms)
         pos = {s: a for a, s in enumerate(atom_syms)}
-        for k, (e, atoms) in enumerate(zip(exprs, grads)):
-            if not atoms:
-                continue
-            node = ilow.lower(e)
-            nodes = [itable[s] for s in atoms]
+        for k, node, nodes in _lower_instance(
+                dag, exprs, atom_syms, grads, parameters[:num_known_par],
+                skip_constants=True):
+            atoms = grads[k]
             g = forward_jacobian(dag, [node], nodes)[0]
             H = forward_jacobian(dag, g, nodes)
             fi = [free_index[pos[s]] for s in atoms]
@@ -357,13 +357,10 @@ def build_hessian_program(discrete_eom, state_cur, state_adj, traj_cur,
 
     return HessianProgram(
         dag=dag, hess_out=out, hess_pairs=pairs, con_out=con_out, jac_out=[],
-        n=n, m=m, q=q, r=r, s=int(variable_duration), M=len(con_out), C=C,
-        num_known_traj=num_known_traj, num_known_par=num_known_par,
-        rows=rows, pars=pars, h=h, method=method,
-        cur_offset=1 if method == 'backward euler' else 0,
-        adj_offset=0 if method == 'backward euler' else 1,
-        inst_hess_out=inst_out, inst_hess_con=inst_con,
-        inst_hess_atoms=inst_atoms, num_inst_atoms=num_atoms)
+        M=len(con_out), C=C, inst_hess_out=inst_out, inst_hess_con=inst_con,
+        inst_hess_atoms=inst_atoms, num_inst_atoms=num_atoms,
+        **_layout(state_cur, traj_cur, num_known_traj, parameters,
+                  num_known_par, variable_duration, method))
 
 
 class JacobianProductProgram(CollocationProgram):
@@ -424,27 +421,10 @@ def build_jacobian_product_program(discrete_eom, state_cur, state_adj,
     the tangent of ``r_i`` is ``dr_i v_x``, the adjoint goes through the
     same ``chain`` as :func:`build_program`'s.  The instance constraints
     contribute their first partials as in the Jacobian program."""
-    dag = ir.DAG()
-    n = len(state_cur)
-    m = len(traj_cur)
-    q = m - num_known_traj
-    r = len(parameters) - num_known_par
-    table = {}
-    for k, s in enumerate(state_cur):
-        table[s] = dag.input('cur', k)
-    for k, s in enumerate(state_adj):
-        table[s] = dag.input('adj', k)
-    for k, s in enumerate(traj_cur):
-        table[s] = dag.input('cur', n + k)
-    if method == 'midpoint':
-        for k, s in enumerate(traj_adj):
-            table[s] = dag.input('adj', n + k)
-    for k, s in enumerate(parameters):
-        table[s] = dag.input('par', k)
-    table[h_sym] = dag.input('h', 0)
-
-    low = Lowerer(dag, table)
-    con_out = [low.lower(e) for e in discrete_eom]
+    dag, table, con_out = _front_end(discrete_eom, state_cur, state_adj,
+                                     traj_cur, traj_adj, parameters, h_sym,
+                                     method)
+    n, q = len(state_cur), len(traj_cur) - num_known_traj
     collect = os.environ.get('OPTY_COLLECT', '1') != '0'
     if collect:
         # the compact form FIRST: both sweeps then differentiate one
@@ -481,41 +461,25 @@ def build_jacobian_product_program(discrete_eom, state_cur, state_adj,
         tan = min(tan, collect_coefficients(dag, list(tan)), key=cost)
         adj = min(adj, collect_coefficients(dag, list(adj)), key=cost)
 
-    rows = [('free', k) for k in range(n)]
-    rows += [('known', j) for j in range(num_known_traj)]
-    rows += [('free', n + j) for j in range(q)]
-    pars = [('known', k) for k in range(num_known_par)]
-    pars += [('tail', j) for j in range(r)]
-    h = ('tail', r) if variable_duration else ('fixed',)
-
     inst_jac_out, inst_pairs, num_atoms, num_inst = [], [], 0, 0
     if instance is not None:
         exprs, atom_syms, grads = instance
-        itable = {s: dag.input('free', a) for a, s in enumerate(atom_syms)}
-        for k, s in enumerate(parameters[:num_known_par]):
-            itable[s] = dag.input('par', k)
-        ilow = Lowerer(dag, itable)
         num_atoms = len(atom_syms)
         num_inst = len(exprs)
         pos = {s: a for a, s in enumerate(atom_syms)}
-        for k, (e, atoms) in enumerate(zip(exprs, grads)):
-            if not atoms:
-                continue
-            node = ilow.lower(e)
-            g = forward_jacobian(dag, [node], [itable[s] for s in atoms])[0]
-            inst_jac_out += g
-            inst_pairs += [(k, pos[s]) for s in atoms]
+        for k, node, nodes in _lower_instance(
+                dag, exprs, atom_syms, grads, parameters[:num_known_par],
+                skip_constants=True):
+            inst_jac_out += forward_jacobian(dag, [node], nodes)[0]
+            inst_pairs += [(k, pos[s]) for s in grads[k]]
 
     return JacobianProductProgram(
         dag=dag, tan_out=tan, adj_out=adj, con_out=con_out, jac_out=[],
         adj_sides=[column_side(n, q, method, k) for k in range(C)],
-        n=n, m=m, q=q, r=r, s=int(variable_duration), M=len(con_out), C=C,
-        num_known_traj=num_known_traj, num_known_par=num_known_par,
-        rows=rows, pars=pars, h=h, method=method,
-        cur_offset=1 if method == 'backward euler' else 0,
-        adj_offset=0 if method == 'backward euler' else 1,
-        inst_jac_out=inst_jac_out, inst_pairs=inst_pairs,
-        num_inst=num_inst, num_inst_atoms=num_atoms)
+        M=len(con_out), C=C, inst_jac_out=inst_jac_out,
+        inst_pairs=inst_pairs, num_inst=num_inst, num_inst_atoms=num_atoms,
+        **_layout(state_cur, traj_cur, num_known_traj, parameters,
+                  num_known_par, variable_duration, method))
 
 
 def assemble_jvp(prog, N, tan, inst, v, atom_free_index):

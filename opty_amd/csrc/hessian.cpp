@@ -28,6 +28,7 @@ struct HessArgs {
     double h;
     long long N;
 };
+static_assert(sizeof(HessArgs) == 64, "HessArgs must match HESS_PARAMS");
 
 // Closed-form indices: entry e of constraint node i has the global indices
 // side(pattern[4e], pattern[4e+1]) and side(pattern[4e+2], pattern[4e+3]),
@@ -57,19 +58,14 @@ opty_hess_indices_kernel(const int *pattern, int PH, long long N,
 
 }  // namespace
 
-struct opty_hip_hessian {
-    opty_hip_problem *p = nullptr;
+struct opty_hip_hessian : Borrowed {
     opty_hip_hessian_desc d{};
-    int device = 0;
-    hipModule_t module = nullptr;
     hipFunction_t k_hess = nullptr, k_inst = nullptr;
     int *d_pattern = nullptr;
     long long *d_irows = nullptr, *d_icols = nullptr;
     // staging for host callers
     double *d_free = nullptr, *d_lam = nullptr, *d_hess = nullptr;
     long long *d_rows = nullptr, *d_cols = nullptr;
-    hipStream_t stream = nullptr;
-    hipStream_t last_stream = nullptr;   // stream of the last enqueued work
     int64_t ncn() const { return p->d.N - 1; }
     int64_t nnz() const { return (int64_t)d.PH*ncn() + d.nnz_inst; }
 };
@@ -93,29 +89,16 @@ int opty_hip_hessian_create(opty_hip_problem *p,
                     "constraints");
     if (int rc = use_device(p)) return rc;
     auto *h = new opty_hip_hessian;
-    h->p = p;
     h->d = *desc;
     h->d.pattern = nullptr;
     h->d.inst_rows = h->d.inst_cols = nullptr;
-    h->device = p->d.device;
-    hipError_t e = hipModuleLoad(&h->module, code_object_path);
-    if (e != hipSuccess) {
+    if (int rc = borrowed_create(
+            h, p, code_object_path,
+            {{&h->k_hess, "opty_hess", desc->PH > 0},
+             {&h->k_inst, "opty_hess_inst", desc->nnz_inst > 0}},
+            "opty_hess/opty_hess_inst")) {
         delete h;
-        (void)hipGetLastError();
-        return fail("hipModuleLoad(%s) failed: %s", code_object_path,
-                    hipGetErrorString(e));
-    }
-    if ((desc->PH > 0 &&
-         hipModuleGetFunction(&h->k_hess, h->module, "opty_hess") !=
-             hipSuccess) ||
-        (desc->nnz_inst > 0 &&
-         hipModuleGetFunction(&h->k_inst, h->module, "opty_hess_inst") !=
-             hipSuccess)) {
-        (void)hipGetLastError();    // not left behind for the caller's runtime
-        (void)hipModuleUnload(h->module);
-        delete h;
-        return fail("opty_hess/opty_hess_inst missing from %s",
-                    code_object_path);
+        return rc;
     }
     auto upload = [&]() -> int {
         if (desc->PH > 0) {
@@ -145,16 +128,9 @@ int opty_hip_hessian_create(opty_hip_problem *p,
 }
 
 int opty_hip_hessian_destroy(opty_hip_hessian *h) {
-    // (touches nothing of the problem handle, which may be gone already)
     if (!h) return 0;
-    (void)hipSetDevice(h->device);
-    if (h->last_stream)
-        (void)hipStreamSynchronize(sync_target(h->last_stream));
-    void *bufs[] = {h->d_pattern, h->d_irows, h->d_icols, h->d_free,
-                    h->d_lam, h->d_hess, h->d_rows, h->d_cols};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->module) (void)hipModuleUnload(h->module);
+    borrowed_destroy(h, {h->d_pattern, h->d_irows, h->d_icols, h->d_free,
+                         h->d_lam, h->d_hess, h->d_rows, h->d_cols});
     delete h;
     return 0;
 }
@@ -166,48 +142,29 @@ int64_t opty_hip_hessian_nnz(const opty_hip_hessian *h) {
 int opty_hip_eval_hess(opty_hip_hessian *h, const double *free_,
                        const double *lagrange, double *hess, int32_t mem) {
     if (!h || !free_ || !lagrange || !hess) return fail("null argument");
-    if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
-        return fail("bad memory kind %d", mem);
     // an even PH is flushed with 16-byte stores at hess + (even offset)
     // (opty_flush16): the caller's device pointer has to allow them
     if (mem == OPTY_HIP_DEVICE && h->d.PH > 0 && h->d.PH % 2 == 0 &&
         (reinterpret_cast<uintptr_t>(hess) & 15) != 0)
         return fail("hess (%p) must be 16-byte aligned in device memory when "
                     "PH (%d) is even", (void *)hess, h->d.PH);
+    if (int rc = borrowed_begin(h, mem, true)) return rc;
     opty_hip_problem *p = h->p;
-    if (int rc = use_device(p)) return rc;
-    if (int rc = check_ready(p)) return rc;
-    // the problem's stream, whichever it is now; the staging buffers may
-    // still be in use on the one of the previous call
-    h->stream = p->stream;
-    if (int rc = order_streams(h)) return rc;
     const long long ncn = h->ncn();
     const size_t nfree = (size_t)p->num_free(), ncon = (size_t)p->num_con(),
                  nnz = (size_t)h->nnz();
-    const double *dfree = free_, *dlam = lagrange;
-    double *dhess = hess;
-    if (mem == OPTY_HIP_HOST) {
-        if (int rc = ensure(&h->d_free, nfree)) return rc;
-        if (int rc = ensure(&h->d_lam, std::max<size_t>(1, ncon))) return rc;
-        if (int rc = ensure(&h->d_hess, std::max<size_t>(1, nnz))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_free, free_, nfree*sizeof(double),
-                               hipMemcpyHostToDevice, h->stream));
-        if (ncon)
-            HIP_TRY(hipMemcpyAsync(h->d_lam, lagrange, ncon*sizeof(double),
-                                   hipMemcpyHostToDevice, h->stream));
-        dfree = h->d_free;
-        dlam = h->d_lam;
-        dhess = h->d_hess;
-    }
     HessArgs a{};
-    a.free_ = dfree;
-    a.known_traj = p->d_known;
-    a.params = p->d_params;
-    a.lam = dlam;
-    a.inst_idx = p->d_inst_idx;
-    a.hess = dhess;
-    a.h = p->h;
-    a.N = p->d.N;
+    a.lam = lagrange;
+    a.hess = hess;
+    if (mem == OPTY_HIP_HOST) {
+        if (int rc = stage_in(h, &free_, &h->d_free, nfree, nfree)) return rc;
+        if (int rc = stage_in(h, &a.lam, &h->d_lam, ncon,
+                              std::max<size_t>(1, ncon)))
+            return rc;
+        if (int rc = ensure(&h->d_hess, std::max<size_t>(1, nnz))) return rc;
+        a.hess = h->d_hess;
+    }
+    borrowed_args(&a, p, free_);
     size_t size = sizeof a;
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
@@ -221,10 +178,9 @@ int opty_hip_eval_hess(opty_hip_hessian *h, const double *free_,
         HIP_TRY(hipModuleLaunchKernel(h->k_inst, 1, 1, 1, 64, 1, 1, 0,
                                       h->stream, nullptr, config));
     if (mem == OPTY_HIP_HOST) {
-        if (nnz)
-            HIP_TRY(hipMemcpyAsync(hess, h->d_hess, nnz*sizeof(double),
-                                   hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(sync_target(h->stream)));
+        if (int rc = stage_out(h, hess, h->d_hess, nnz*sizeof(double)))
+            return rc;
+        return host_done(h);
     }
     return 0;
 }
@@ -232,12 +188,8 @@ int opty_hip_eval_hess(opty_hip_hessian *h, const double *free_,
 int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
                              int64_t *cols, int32_t mem) {
     if (!h || !rows || !cols) return fail("null argument");
-    if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
-        return fail("bad memory kind %d", mem);
+    if (int rc = borrowed_begin(h, mem, false)) return rc;
     opty_hip_problem *p = h->p;
-    if (int rc = use_device(p)) return rc;
-    h->stream = p->stream;
-    if (int rc = order_streams(h)) return rc;
     const long long ncn = h->ncn();
     const size_t nnz = (size_t)h->nnz();
     long long *dr = (long long *)rows, *dc = (long long *)cols;
@@ -257,13 +209,11 @@ int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
         HIP_TRY(hipGetLastError());
     }
     if (mem == OPTY_HIP_HOST) {
-        if (nnz) {
-            HIP_TRY(hipMemcpyAsync(rows, h->d_rows, nnz*sizeof(long long),
-                                   hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(cols, h->d_cols, nnz*sizeof(long long),
-                                   hipMemcpyDeviceToHost, h->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(sync_target(h->stream)));
+        if (int rc = stage_out(h, rows, h->d_rows, nnz*sizeof(long long)))
+            return rc;
+        if (int rc = stage_out(h, cols, h->d_cols, nnz*sizeof(long long)))
+            return rc;
+        return host_done(h);
     }
     return 0;
 }

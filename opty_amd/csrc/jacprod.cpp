@@ -30,6 +30,8 @@ struct JacprodArgs {
     double h;
     long long N;
 };
+static_assert(sizeof(JacprodArgs) == 72,
+              "JacprodArgs must match JACPROD_PARAMS");
 
 // constraint nodes a block of opty_vjp advances by (VJP_STRIDE of
 // emit_jacprod.py): 64 lanes, the first repeats the previous block's last
@@ -37,18 +39,13 @@ constexpr long long kVjpStride = 63;
 
 }  // namespace
 
-struct opty_hip_jacprod {
-    opty_hip_problem *p = nullptr;
+struct opty_hip_jacprod : Borrowed {
     opty_hip_jacprod_desc d{};
-    int device = 0;
-    hipModule_t module = nullptr;
     hipFunction_t k_jvp = nullptr, k_jvp_inst = nullptr, k_vjp = nullptr,
                   k_vjp_fin = nullptr;
     double *d_part = nullptr;   // num_tail partials per block of opty_vjp
     // staging for host callers
     double *d_free = nullptr, *d_vec = nullptr, *d_out = nullptr;
-    hipStream_t stream = nullptr;
-    hipStream_t last_stream = nullptr;   // stream of the last enqueued work
     long long ncn() const { return p->d.N - 1; }
     long long vjp_blocks() const {
         return (ncn() + kVjpStride - 1)/kVjpStride;
@@ -57,64 +54,37 @@ struct opty_hip_jacprod {
 
 namespace {
 
-int prepare(opty_hip_jacprod *h, const double *free_, const double *vec,
-            double *out, int32_t mem) {
-    if (!h || !free_ || !vec || !out) return fail("null argument");
-    if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
-        return fail("bad memory kind %d", mem);
-    opty_hip_problem *p = h->p;
-    if (int rc = use_device(p)) return rc;
-    if (int rc = check_ready(p)) return rc;
-    // the problem's stream, whichever it is now; the staging buffers may
-    // still be in use on the one of the previous call
-    h->stream = p->stream;
-    return order_streams(h);
-}
-
 // One product: `nvec` doubles of `vec` in, `nout` doubles out.
 template <typename Launch>
 int run(opty_hip_jacprod *h, const double *free_, const double *vec,
         size_t nvec, double *out, size_t nout, int32_t mem, Launch launch) {
+    if (!h || !free_ || !vec || !out) return fail("null argument");
+    if (int rc = borrowed_begin(h, mem, true)) return rc;
     opty_hip_problem *p = h->p;
     const size_t nfree = (size_t)p->num_free();
-    const double *dfree = free_, *dvec = vec;
-    double *dout = out;
+    JacprodArgs a{};
+    a.vec = vec;
+    a.out = out;
+    a.part = h->d_part;
     if (mem == OPTY_HIP_HOST) {
         // one staging vector each, sized for either product
         const size_t big = std::max<size_t>(
             1, std::max(nfree, (size_t)p->num_con()));
-        if (int rc = ensure(&h->d_free, nfree)) return rc;
-        if (int rc = ensure(&h->d_vec, big)) return rc;
+        if (int rc = stage_in(h, &free_, &h->d_free, nfree, nfree)) return rc;
+        if (int rc = stage_in(h, &a.vec, &h->d_vec, nvec, big)) return rc;
         if (int rc = ensure(&h->d_out, big)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_free, free_, nfree*sizeof(double),
-                               hipMemcpyHostToDevice, h->stream));
-        if (nvec)
-            HIP_TRY(hipMemcpyAsync(h->d_vec, vec, nvec*sizeof(double),
-                                   hipMemcpyHostToDevice, h->stream));
-        dfree = h->d_free;
-        dvec = h->d_vec;
-        dout = h->d_out;
+        a.out = h->d_out;
     }
-    JacprodArgs a{};
-    a.free_ = dfree;
-    a.known_traj = p->d_known;
-    a.params = p->d_params;
-    a.vec = dvec;
-    a.inst_idx = p->d_inst_idx;
-    a.out = dout;
-    a.part = h->d_part;
-    a.h = p->h;
-    a.N = p->d.N;
+    borrowed_args(&a, p, free_);
     size_t size = sizeof a;
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                       HIP_LAUNCH_PARAM_END};
     if (int rc = launch(config)) return rc;
     if (mem == OPTY_HIP_HOST) {
-        if (nout)
-            HIP_TRY(hipMemcpyAsync(out, h->d_out, nout*sizeof(double),
-                                   hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(sync_target(h->stream)));
+        if (int rc = stage_out(h, out, h->d_out, nout*sizeof(double)))
+            return rc;
+        return host_done(h);
     }
     return 0;
 }
@@ -144,26 +114,16 @@ int opty_hip_jacprod_create(opty_hip_problem *p,
     if (p->d.N < 2) return fail("N %lld < 2", (long long)p->d.N);
     if (int rc = use_device(p)) return rc;
     auto *h = new opty_hip_jacprod;
-    h->p = p;
     h->d = *desc;
-    h->device = p->d.device;
-    hipError_t e = hipModuleLoad(&h->module, code_object_path);
-    if (e != hipSuccess) {
+    if (int rc = borrowed_create(h, p, code_object_path,
+                                 {{&h->k_jvp, "opty_jvp", true},
+                                  {&h->k_jvp_inst, "opty_jvp_inst", true},
+                                  {&h->k_vjp, "opty_vjp", true},
+                                  {&h->k_vjp_fin, "opty_vjp_fin", true}},
+                                 nullptr)) {
         delete h;
-        (void)hipGetLastError();
-        return fail("hipModuleLoad(%s) failed: %s", code_object_path,
-                    hipGetErrorString(e));
+        return rc;
     }
-    struct { hipFunction_t *f; const char *name; } wanted[] = {
-        {&h->k_jvp, "opty_jvp"}, {&h->k_jvp_inst, "opty_jvp_inst"},
-        {&h->k_vjp, "opty_vjp"}, {&h->k_vjp_fin, "opty_vjp_fin"}};
-    for (auto &w : wanted)
-        if (hipModuleGetFunction(w.f, h->module, w.name) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipModuleUnload(h->module);
-            delete h;
-            return fail("%s missing from %s", w.name, code_object_path);
-        }
     if (desc->num_tail > 0) {
         // one partial per block of opty_vjp and tail column
         hipError_t m = hipMalloc(
@@ -181,22 +141,15 @@ int opty_hip_jacprod_create(opty_hip_problem *p,
 }
 
 int opty_hip_jacprod_destroy(opty_hip_jacprod *h) {
-    // (touches nothing of the problem handle, which may be gone already)
     if (!h) return 0;
-    (void)hipSetDevice(h->device);
-    if (h->last_stream)
-        (void)hipStreamSynchronize(sync_target(h->last_stream));
-    void *bufs[] = {h->d_part, h->d_free, h->d_vec, h->d_out};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->module) (void)hipModuleUnload(h->module);
+    borrowed_destroy(h, {h->d_part, h->d_free, h->d_vec, h->d_out});
     delete h;
     return 0;
 }
 
 int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free_,
                          const double *v, double *out, int32_t mem) {
-    if (int rc = prepare(h, free_, v, out, mem)) return rc;
+    if (!h) return fail("null argument");
     opty_hip_problem *p = h->p;
     const long long nblk = (h->ncn() + 63)/64;
     return run(h, free_, v, (size_t)p->num_free(), out, (size_t)p->num_con(),
@@ -214,7 +167,7 @@ int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free_,
 
 int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free_,
                          const double *w, double *out, int32_t mem) {
-    if (int rc = prepare(h, free_, w, out, mem)) return rc;
+    if (!h) return fail("null argument");
     opty_hip_problem *p = h->p;
     return run(h, free_, w, (size_t)p->num_con(), out, (size_t)p->num_free(),
                mem, [&](void **config) -> int {

@@ -1,6 +1,7 @@
 // opty_internal.h -- what the translation units of libopty_hip.so share:
 // error reporting, the problem handle, the launch / evaluation core's
-// prototypes.  Not installed; the public interface is include/opty_hip.h.
+// prototypes, the base of the handles that borrow a problem handle.  Not
+// installed; the public interface is include/opty_hip.h.
 //
 //   runtime.cpp       handles, kernel launches, routing, the entry points of
 //                     the evaluation itself, index kernels, objective and
@@ -30,6 +31,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <queue>
 #include <string>
@@ -230,6 +232,112 @@ int ensure_pinned(T **ptr, size_t count) {
         HIP_TRY(pinned_alloc(reinterpret_cast<void **>(ptr),
                              count*sizeof(T)));
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Handles that BORROW a problem handle (hessian.cpp, jacprod.cpp): a code
+// object of their own, launched on the problem's device data (known
+// parameters and trajectories, h, instance atom indices) and on the problem's
+// stream, whichever it is at the time of the call.  They embed this base as
+// their first base class and add their kernels, descriptor and buffers.
+struct Borrowed {
+    opty_hip_problem *p = nullptr;
+    int device = 0;
+    hipModule_t module = nullptr;
+    hipStream_t stream = nullptr;
+    hipStream_t last_stream = nullptr;   // stream of the last enqueued work
+};
+
+struct WantedKernel {
+    hipFunction_t *f;
+    const char *name;
+    bool required;
+};
+
+// Loads the code object and looks the kernels up.  `label`: what the message
+// of a missing kernel names (null: the kernel itself).  On failure nothing is
+// left loaded; the caller deletes its handle.
+inline int borrowed_create(Borrowed *b, opty_hip_problem *p, const char *path,
+                           std::initializer_list<WantedKernel> wanted,
+                           const char *label) {
+    b->p = p;
+    b->device = p->d.device;
+    hipError_t e = hipModuleLoad(&b->module, path);
+    if (e != hipSuccess) {
+        b->module = nullptr;
+        (void)hipGetLastError();
+        return fail("hipModuleLoad(%s) failed: %s", path,
+                    hipGetErrorString(e));
+    }
+    for (const WantedKernel &w : wanted)
+        if (w.required &&
+            hipModuleGetFunction(w.f, b->module, w.name) != hipSuccess) {
+            (void)hipGetLastError();    // not left behind for the caller's runtime
+            (void)hipModuleUnload(b->module);
+            b->module = nullptr;
+            return fail("%s missing from %s", label ? label : w.name, path);
+        }
+    return 0;
+}
+
+// Start of every call: the memory kind, the problem's device, (ready: its
+// tables are installed,) and the problem's stream, whichever it is now -- the
+// staging buffers may still be in use on the one of the previous call.
+inline int borrowed_begin(Borrowed *b, int32_t mem, bool ready) {
+    if (mem != OPTY_HIP_HOST && mem != OPTY_HIP_DEVICE)
+        return fail("bad memory kind %d", mem);
+    if (int rc = use_device(b->p)) return rc;
+    if (ready)
+        if (int rc = check_ready(b->p)) return rc;
+    b->stream = b->p->stream;
+    return order_streams(b);
+}
+
+// Host callers: `count` values of the host vector `*ptr` go to the staging
+// vector `*dev` (allocated once, `room` values), which `*ptr` then names.
+inline int stage_in(Borrowed *b, const double **ptr, double **dev,
+                    size_t count, size_t room) {
+    if (int rc = ensure(dev, room)) return rc;
+    if (count)
+        HIP_TRY(hipMemcpyAsync(*dev, *ptr, count*sizeof(double),
+                               hipMemcpyHostToDevice, b->stream));
+    *ptr = *dev;
+    return 0;
+}
+
+// ... and the way back; host_done waits for the copies.
+inline int stage_out(Borrowed *b, void *host, const void *dev, size_t bytes) {
+    if (bytes)
+        HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost,
+                               b->stream));
+    return 0;
+}
+
+inline int host_done(Borrowed *b) {
+    HIP_TRY(hipStreamSynchronize(sync_target(b->stream)));
+    return 0;
+}
+
+// The fields every derived kernel's packed arguments share.
+template <typename Args>
+void borrowed_args(Args *a, const opty_hip_problem *p, const double *dfree) {
+    a->free_ = dfree;
+    a->known_traj = p->d_known;
+    a->params = p->d_params;
+    a->inst_idx = p->d_inst_idx;
+    a->h = p->h;
+    a->N = p->d.N;
+}
+
+// Waits for the handle's last work, frees `bufs` and unloads the module
+// (touches nothing of the problem handle, which may be gone already).
+inline void borrowed_destroy(Borrowed *b, std::initializer_list<void *> bufs) {
+    (void)hipSetDevice(b->device);
+    if (b->last_stream)
+        (void)hipStreamSynchronize(sync_target(b->last_stream));
+    for (void *buf : bufs)
+        if (buf) (void)hipFree(buf);
+    if (b->module) (void)hipModuleUnload(b->module);
 }
 
 }  // namespace opty

@@ -565,31 +565,45 @@ class ConstraintCollocator(object):
             wrt += (self.time_interval_symbol,)
         return wrt
 
+    def _instance_placeholders(self, with_free_index=False):
+        """The instance constraints written over one placeholder Symbol per
+        function atom, as the program builders take them: ``(expressions,
+        atom symbols, atoms per expression[, free index per atom])``; None
+        without instance constraints."""
+        if self.instance_constraints is None:
+            return None
+        place = {f: sm.Symbol('opty_atom_%d' % a, real=True)
+                 for a, f in enumerate(self._inst_atoms)}
+        exprs = [sm.sympify(c).xreplace(place)
+                 for c in self.instance_constraints]
+        grads = [[place[f] for f in atoms]
+                 for atoms in self._inst_atoms_per_constraint]
+        instance = (exprs, [place[f] for f in self._inst_atoms], grads)
+        if with_free_index:
+            instance += (self._atom_free_index(),)
+        return instance
+
+    def _builder_arguments(self):
+        """The positional arguments the three program builders share (up to
+        and including ``method``)."""
+        be = self.integration_method == 'backward euler'
+        return (list(self.discrete_eom),
+                self.current_discrete_state_symbols,
+                self.previous_discrete_state_symbols if be
+                else self.next_discrete_state_symbols,
+                self.current_discrete_specified_symbols,
+                self.next_discrete_specified_symbols,
+                self.num_known_input_trajectories,
+                self.parameters, self.num_known_parameters,
+                self.time_interval_symbol, self._variable_duration,
+                self._wrt(), self.integration_method)
+
     def _build_program(self):
         if self._program is not None:
             return self._program
-        be = self.integration_method == 'backward euler'
-        instance = None
-        if self.instance_constraints is not None:
-            place = {f: sm.Symbol('opty_atom_%d' % a, real=True)
-                     for a, f in enumerate(self._inst_atoms)}
-            exprs = [sm.sympify(c).xreplace(place)
-                     for c in self.instance_constraints]
-            grads = [[place[f] for f in atoms]
-                     for atoms in self._inst_atoms_per_constraint]
-            instance = (exprs, [place[f] for f in self._inst_atoms], grads)
         logger.info('Lowering and differentiating the constraint function.')
         self._program = build_program(
-            list(self.discrete_eom),
-            self.current_discrete_state_symbols,
-            self.previous_discrete_state_symbols if be
-            else self.next_discrete_state_symbols,
-            self.current_discrete_specified_symbols,
-            self.next_discrete_specified_symbols,
-            self.num_known_input_trajectories,
-            self.parameters, self.num_known_parameters,
-            self.time_interval_symbol, self._variable_duration,
-            self._wrt(), self.integration_method, instance,
+            *self._builder_arguments(), self._instance_placeholders(),
             implicit=self._implicit_chain(), prune_zeros=self._prune_zeros,
             layout='csr' if self._jacobian_layout == 'csr' else 'coo')
         return self._program
@@ -606,31 +620,11 @@ class ConstraintCollocator(object):
             raise NotImplementedError(
                 'the Hessian of a problem with known trajectories given as '
                 'functions of the free vector is not available.')
-        be = self.integration_method == 'backward euler'
-        instance = None
-        if self.instance_constraints is not None:
-            place = {f: sm.Symbol('opty_atom_%d' % a, real=True)
-                     for a, f in enumerate(self._inst_atoms)}
-            exprs = [sm.sympify(c).xreplace(place)
-                     for c in self.instance_constraints]
-            grads = [[place[f] for f in atoms]
-                     for atoms in self._inst_atoms_per_constraint]
-            idx = self.instance_constraints_free_index_map
-            instance = (exprs, [place[f] for f in self._inst_atoms], grads,
-                        [idx[f] for f in self._inst_atoms])
         logger.info('Lowering and differentiating the constraint '
                     'Lagrangian twice.')
         self._hessian_program = build_hessian_program(
-            list(self.discrete_eom),
-            self.current_discrete_state_symbols,
-            self.previous_discrete_state_symbols if be
-            else self.next_discrete_state_symbols,
-            self.current_discrete_specified_symbols,
-            self.next_discrete_specified_symbols,
-            self.num_known_input_trajectories,
-            self.parameters, self.num_known_parameters,
-            self.time_interval_symbol, self._variable_duration,
-            self._wrt(), self.integration_method, instance,
+            *self._builder_arguments(),
+            self._instance_placeholders(with_free_index=True),
             implicit=self._implicit_chain())
         return self._hessian_program
 
@@ -645,13 +639,28 @@ class ConstraintCollocator(object):
         (a hit: the uniform-sincos sibling is built in its place when it is
         clean).  A module that spills whatever the cut is refused."""
         from .codegen.emit_hessian import emit_hessian_module
+        hsaco, cut, meta = self._build_spill_free_module(
+            emit_hessian_module, self._build_hessian_program(),
+            ('opty_hess', 'opty_hess_inst'), self._HESS_STRIP_OPS)
+        if hsaco is None:
+            raise hb.HipBackendError(
+                'every build of the Hessian kernels spills vector registers: '
+                '%s' % meta['tried'])
+        return hsaco, cut, dict(meta, strips=len(cut))
+
+    def _build_spill_free_module(self, emit, prog, names, budget):
+        """``(hsaco, cut(s), meta)`` of a derived program's module, from
+        ``emit(prog, budget, forget, fast_trig=1) -> (source, cut(s))``: the
+        first build whose kernels ``names`` spill no vector register (the
+        strip budget halved down to 200, then ``forget``; six tries), through
+        the static ISA check (a hit: the uniform-sincos sibling is built in
+        its place when it is clean).  ``hsaco`` is None and ``meta['tried']``
+        lists the builds when every one of them spills."""
         from . import isa_check
-        prog = self._build_hessian_program()
-        names = ('opty_hess', 'opty_hess_inst')
-        budget, forget = self._HESS_STRIP_OPS, False
+        forget = False
         tried = []
         for _ in range(6):
-            source, cut = emit_hessian_module(prog, budget, forget)
+            source, cut = emit(prog, budget, forget)
             hsaco = self._compile(source)
             spills = hb.vgpr_spills(hsaco, names)
             tried.append((budget, forget, spills))
@@ -662,18 +671,16 @@ class ConstraintCollocator(object):
             else:
                 forget = True
         else:
-            raise hb.HipBackendError(
-                'every build of the Hessian kernels spills vector registers: '
-                '%s' % tried)
+            return None, None, dict(tried=tried)
         hits = isa_check.exec_copies(hsaco, names)
         if hits:
-            src2, cut2 = emit_hessian_module(prog, budget, forget, fast_trig=2)
+            src2, cut2 = emit(prog, budget, forget, fast_trig=2)
             twin = self._compile(src2)
             if not hb.vgpr_spills(twin, names) and \
                     not isa_check.exec_copies(twin, names):
                 hsaco, cut, hits = twin, cut2, {}
-        return hsaco, cut, dict(strips=len(cut), strip_ops=budget,
-                                forget=forget, isa_exec_copies=hits)
+        return hsaco, cut, dict(strip_ops=budget, forget=forget,
+                                isa_exec_copies=hits)
 
     #: constraint nodes the referee compares: the first wave and the last node
     _HESS_VERIFY_NODES = 64
@@ -684,8 +691,6 @@ class ConstraintCollocator(object):
         start as NaN, against the DAG as an instruction tape on the GPU
         (``opty_hip_tape_run``) on a node window, to 64 units of each entry's
         own rounding-error bound.  Raises :class:`hip_backend.BuildRejected`."""
-        from .codegen.tape import Tape
-        from .codegen.errbound import evaluate_with_error_bound
         prog = self._build_hessian_program()
         N = self.num_collocation_nodes
         ncn = N - 1
@@ -708,16 +713,10 @@ class ConstraintCollocator(object):
                                 ncn - 1])
         inputs = self._hessian_inputs(free, lam, nodes)
         roots = list(prog.hess_out) + list(prog.inst_hess_out)
-        tape = Tape(prog.dag, roots)
-        vals = hb.tape_run(tape, tape.table(len(nodes), inputs), self._device)
-        _, bound = evaluate_with_error_bound(prog.dag, roots, inputs)
+        val, bnd = self._tape_referee(prog, roots, inputs, len(nodes))
         PH = prog.PH
-        u = 2.0**-53
         worst = 0.0
-        for e, node in enumerate(roots):
-            want = vals[tape.slot[node]]
-            b = np.broadcast_to(np.abs(np.asarray(bound[e], dtype=float)),
-                                want.shape)
+        for e, (want, b) in enumerate(zip(val, bnd)):
             if e < PH:
                 have = got[nodes*PH + e]
             else:
@@ -725,72 +724,86 @@ class ConstraintCollocator(object):
                 scale = lam[prog.M*ncn + prog.inst_hess_con[t]]
                 have = np.full(want.shape, got[ncn*PH + t])
                 want, b = want*scale, b*abs(scale)
-            err = np.abs(have - want)
-            tol = 64.0*u*b + 4.0*u*np.abs(want)
-            if not np.all(err <= tol):
-                raise hb.BuildRejected(
-                    'Hessian entry %d disagrees with the instruction tape '
-                    '(max error %.3g)' % (e, np.nanmax(err)),
-                    dict(entry=e, err=float(np.nanmax(err))))
-            worst = max(worst, float(np.max(err/np.maximum(tol, 1e-300))))
+            worst = max(worst, self._tape_check(
+                'Hessian entry %d' % e, have, want, b, np.abs(want),
+                entry=e))
         return dict(ok=True, referee='tape', nodes=len(nodes),
                     worst_fraction_of_tolerance=worst)
+
+    def _tape_referee(self, prog, roots, inputs, count):
+        """Values of ``roots`` from the DAG of ``prog`` run as an instruction
+        tape on the GPU (``opty_hip_tape_run``) at ``count`` nodes, and their
+        rounding-error bounds: ``(len(roots), count)`` each."""
+        from .codegen.tape import Tape
+        from .codegen.errbound import evaluate_with_error_bound
+        if not roots:
+            return np.zeros((0, count)), np.zeros((0, count))
+        tape = Tape(prog.dag, roots)
+        vals = hb.tape_run(tape, tape.table(count, inputs), self._device)
+        _, bound = evaluate_with_error_bound(prog.dag, roots, inputs)
+        val = np.stack([vals[tape.slot[r]] for r in roots])
+        bnd = np.stack([np.broadcast_to(np.abs(np.asarray(
+            b, dtype=float)), (count,)) for b in bound])
+        return val, bnd
+
+    @staticmethod
+    def _tape_check(subject, have, want, bnd, mag, **key):
+        """Holds ``have`` to the referee's ``want``: 64 units of the entries'
+        own rounding-error bounds ``bnd`` plus 4 units of ``mag``.  Returns
+        the worst error as a fraction of the tolerance; raises
+        :class:`hip_backend.BuildRejected` (its verdict: ``key`` and the
+        error)."""
+        u = 2.0**-53
+        err = np.abs(have - want)
+        tol = 64.0*u*bnd + 4.0*u*mag
+        if not np.all(err <= tol):
+            raise hb.BuildRejected(
+                '%s disagrees with the instruction tape (max error %.3g)'
+                % (subject, np.nanmax(err)),
+                dict(key, err=float(np.nanmax(err))))
+        return float(np.max(err/np.maximum(tol, 1e-300))) if err.size else 0.0
 
     def _hessian_inputs(self, free, lagrange, nodes):
         """``inputs(kind, index)`` of the Hessian DAG at the constraint nodes
         ``nodes`` (an index array) for ``free`` and ``lagrange``."""
-        prog = self._build_hessian_program()
-        N = self.num_collocation_nodes
-        ncn = N - 1
-        n, q = prog.n, prog.q
-        tail = free[(n + q)*N:]
-        known = self._known_trajectory_array(free) \
-            if self.num_known_input_trajectories else None
-        kpar = [float(self.known_parameter_map[p])
-                for p in self.known_parameters]
-        idx = self.instance_constraints_free_index_map \
-            if self.num_instance_constraints else {}
-
-        def inputs(kind, k):
-            if kind in ('cur', 'adj'):
-                src, r = prog.rows[k]
-                row = free[r*N:(r + 1)*N] if src == 'free' else known[r]
-                off = prog.cur_offset if kind == 'cur' else prog.adj_offset
-                return row[nodes + off]
-            if kind == 'lam':
-                return lagrange[k*ncn + nodes]
-            if kind == 'par':
-                src, r = prog.pars[k]
-                return kpar[r] if src == 'known' else tail[r]
-            if kind == 'h':
-                return self.node_time_interval if prog.h[0] == 'fixed' \
-                    else tail[prog.h[1]]
-            assert kind == 'free', kind
-            return free[idx[self._inst_atoms[k]]]
-        return inputs
+        ncn = self.num_collocation_nodes - 1
+        base = self._shared_inputs(self._build_hessian_program(), free, nodes)
+        return lambda kind, k: lagrange[k*ncn + nodes] if kind == 'lam' \
+            else base(kind, k)
 
     def _ensure_hessian(self):
         """The Hessian handle (built, checked and verified on first use; it
         borrows the problem handle's device data)."""
-        if getattr(self, '_hessian', None) is not None:
-            return self._hessian
+        def create(hip):
+            prog = self._build_hessian_program()
+            hsaco, cut, meta = self._build_hessian_code_object()
+            rows, cols = self.hessian_indices_closed_form()
+            PH, ncn = prog.PH, self.num_collocation_nodes - 1
+            return hb.HipHessian(hip, dict(
+                PH=PH, nnz_inst=len(prog.inst_hess_out),
+                strips=max(1, len(cut)),
+                pattern=np.array(prog.index_pattern(), dtype=np.int32),
+                inst_rows=rows[ncn*PH:], inst_cols=cols[ncn*PH:]),
+                hsaco), dict(meta, hsaco=hsaco)
+        return self._ensure_derived('_hessian', create, self._verify_hessian)
+
+    def _ensure_derived(self, attr, create, verify):
+        """The handle ``self.<attr>`` of a derived program, made on first use:
+        ``create(hip) -> (handle, meta)`` builds it on the problem handle,
+        ``verify(handle)`` holds it to its DAG (a refused handle is
+        released); ``self.<attr>_meta`` records ``meta`` and the verdict."""
+        if getattr(self, attr, None) is not None:
+            return getattr(self, attr)
         hip = self._ensure_hip()
-        prog = self._build_hessian_program()
-        hsaco, cut, meta = self._build_hessian_code_object()
-        rows, cols = self.hessian_indices_closed_form()
-        PH, ncn = prog.PH, self.num_collocation_nodes - 1
-        handle = hb.HipHessian(hip, dict(
-            PH=PH, nnz_inst=len(prog.inst_hess_out), strips=max(1, len(cut)),
-            pattern=np.array(prog.index_pattern(), dtype=np.int32),
-            inst_rows=rows[ncn*PH:], inst_cols=cols[ncn*PH:]), hsaco)
+        handle, meta = create(hip)
         self._sync_known(hip, None)
         try:
-            verdict = self._verify_hessian(handle)
+            verdict = verify(handle)
         except hb.BuildRejected:
             handle.release()
             raise
-        self._hessian_meta = dict(meta, hsaco=hsaco, verdict=verdict)
-        self._hessian = handle
+        setattr(self, attr + '_meta', dict(meta, verdict=verdict))
+        setattr(self, attr, handle)
         return handle
 
     def generate_hessian_function(self):
@@ -808,36 +821,8 @@ class ConstraintCollocator(object):
         ``free`` and ``lagrange`` may also be torch CUDA tensors; the result
         is then a new CUDA tensor (nothing crosses PCIe)."""
         handle = self._ensure_hessian()
-        hip = self._hip
-        result = hb.pinned_empty(handle.nnz)
-        ncon = self.num_constraints
-
-        def hessian(free, lagrange):
-            if hasattr(free, 'data_ptr'):
-                import torch
-                if tuple(free.shape) != (self.num_free,) or \
-                        tuple(lagrange.shape) != (ncon,):
-                    raise ValueError('free / lagrange have the wrong shape')
-                free = free.to(torch.float64).contiguous()
-                lagrange = lagrange.to(device=free.device,
-                                       dtype=torch.float64).contiguous()
-                self._sync_known(hip, None)
-                out = torch.empty(handle.nnz, dtype=torch.float64,
-                                  device=free.device)
-                torch.cuda.current_stream(free.device).synchronize()
-                handle.evaluate(free, lagrange, out, hb.DEVICE)
-                hip.synchronize()
-                return out
-            free = self._host_free(free)
-            lam = np.ascontiguousarray(lagrange, dtype=np.float64)
-            if lam.shape != (ncon,):
-                raise ValueError('lagrange must have shape ({},), got {}'
-                                 .format(ncon, lam.shape))
-            self._sync_known(hip, free)
-            handle.evaluate(free, lam, result, hb.HOST)
-            return result
-        hessian.handle = handle
-        return hessian
+        return self._derived_function(handle, handle.evaluate, 'lagrange',
+                                      self.num_constraints, handle.nnz)
 
     def hessian_indices(self):
         """Row and column indices (int64, row >= col) of every value
@@ -870,29 +855,10 @@ class ConstraintCollocator(object):
         built on first use."""
         if getattr(self, '_jacprod_program', None) is not None:
             return self._jacprod_program
-        be = self.integration_method == 'backward euler'
-        instance = None
-        if self.instance_constraints is not None:
-            place = {f: sm.Symbol('opty_atom_%d' % a, real=True)
-                     for a, f in enumerate(self._inst_atoms)}
-            exprs = [sm.sympify(c).xreplace(place)
-                     for c in self.instance_constraints]
-            grads = [[place[f] for f in atoms]
-                     for atoms in self._inst_atoms_per_constraint]
-            instance = (exprs, [place[f] for f in self._inst_atoms], grads)
         logger.info('Lowering the tangent and the adjoint of the constraint '
                     'function.')
         self._jacprod_program = build_jacobian_product_program(
-            list(self.discrete_eom),
-            self.current_discrete_state_symbols,
-            self.previous_discrete_state_symbols if be
-            else self.next_discrete_state_symbols,
-            self.current_discrete_specified_symbols,
-            self.next_discrete_specified_symbols,
-            self.num_known_input_trajectories,
-            self.parameters, self.num_known_parameters,
-            self.time_interval_symbol, self._variable_duration,
-            self._wrt(), self.integration_method, instance,
+            *self._builder_arguments(), self._instance_placeholders(),
             implicit=self._implicit_chain())
         return self._jacprod_program
 
@@ -908,7 +874,7 @@ class ConstraintCollocator(object):
         prog = self._build_jacprod_program()
         N = self.num_collocation_nodes
         ncn = N - 1
-        base = self._hessian_like_inputs(prog, free, nodes)
+        base = self._shared_inputs(prog, free, nodes)
         vtail = vec[(prog.n + prog.q)*N:] if what == 'jvp' else None
 
         def inputs(kind, k):
@@ -926,7 +892,7 @@ class ConstraintCollocator(object):
             return base(kind, k)
         return inputs
 
-    def _hessian_like_inputs(self, prog, free, nodes):
+    def _shared_inputs(self, prog, free, nodes):
         """``inputs(kind, index)`` for the kinds every program shares
         (``cur``, ``adj``, ``par``, ``h``, ``free``) at the nodes ``nodes``."""
         N = self.num_collocation_nodes
@@ -969,37 +935,15 @@ class ConstraintCollocator(object):
         uniform-sincos sibling is built in its place when it is clean).  A
         module that spills whatever the cut is refused."""
         from .codegen.emit_jacprod import emit_jacprod_module
-        from . import isa_check
-        prog = self._build_jacprod_program()
-        names = self._JACPROD_KERNELS
-        budget, forget = self._JACPROD_STRIP_OPS, False
-        tried = []
-        for _ in range(6):
-            source, cuts = emit_jacprod_module(prog, budget, forget)
-            hsaco = self._compile(source)
-            spills = hb.vgpr_spills(hsaco, names)
-            tried.append((budget, forget, spills))
-            if not spills:
-                break
-            if budget > 200:
-                budget //= 2
-            else:
-                forget = True
-        else:
+        hsaco, cuts, meta = self._build_spill_free_module(
+            emit_jacprod_module, self._build_jacprod_program(),
+            self._JACPROD_KERNELS, self._JACPROD_STRIP_OPS)
+        if hsaco is None:
             raise hb.BuildRejected(
                 'every build of the Jacobian-product kernels spills vector '
-                'registers: %s' % tried, dict(tried=tried))
-        hits = isa_check.exec_copies(hsaco, names)
-        if hits:
-            src2, cuts2 = emit_jacprod_module(prog, budget, forget,
-                                              fast_trig=2)
-            twin = self._compile(src2)
-            if not hb.vgpr_spills(twin, names) and \
-                    not isa_check.exec_copies(twin, names):
-                hsaco, cuts, hits = twin, cuts2, {}
-        return hsaco, dict(jvp_strips=max(1, len(cuts[0])),
-                           vjp_strips=max(1, len(cuts[1])), strip_ops=budget,
-                           forget=forget, isa_exec_copies=hits)
+                'registers: %s' % meta['tried'], meta)
+        return hsaco, dict(meta, jvp_strips=max(1, len(cuts[0])),
+                           vjp_strips=max(1, len(cuts[1])))
 
     #: constraint nodes the referee compares: the first two blocks of
     #: ``opty_vjp`` (both sides of a block edge), the last two nodes and the
@@ -1015,12 +959,9 @@ class ConstraintCollocator(object):
         (``opty_hip_tape_run``) on a node window -- the tail columns of ``J^T
         w`` on all nodes -- to 64 units of each entry's own rounding-error
         bound.  Raises :class:`hip_backend.BuildRejected`."""
-        from .codegen.tape import Tape
-        from .codegen.errbound import evaluate_with_error_bound
         prog = self._build_jacprod_program()
         N = self.num_collocation_nodes
         ncn, M = N - 1, prog.M
-        u = 2.0**-53
         rng = np.random.default_rng(19)
         free = rng.uniform(-1.0, 1.0, self.num_free)
         if self._variable_duration:
@@ -1052,29 +993,11 @@ class ConstraintCollocator(object):
         worst = [0.0]
 
         def check(what, have, want, bnd, mag):
-            err = np.abs(have - want)
-            tol = 64.0*u*bnd + 4.0*u*mag
-            if not np.all(err <= tol):
-                raise hb.BuildRejected(
-                    '%s disagrees with the instruction tape (max error %.3g)'
-                    % (what, np.nanmax(err)),
-                    dict(what=what, err=float(np.nanmax(err))))
-            if err.size:
-                worst[0] = max(worst[0], float(np.max(
-                    err/np.maximum(tol, 1e-300))))
+            worst[0] = max(worst[0], self._tape_check(what, have, want, bnd,
+                                                      mag, what=what))
 
         def referee(roots, inputs, count):
-            """Tape values and error bounds of ``roots``, ``(len(roots),
-            count)`` each."""
-            if not roots:
-                return np.zeros((0, count)), np.zeros((0, count))
-            tape = Tape(prog.dag, roots)
-            vals = hb.tape_run(tape, tape.table(count, inputs), self._device)
-            _, bound = evaluate_with_error_bound(prog.dag, roots, inputs)
-            val = np.stack([vals[tape.slot[r]] for r in roots])
-            bnd = np.stack([np.broadcast_to(np.abs(np.asarray(
-                b, dtype=float)), (count,)) for b in bound])
-            return val, bnd
+            return self._tape_referee(prog, roots, inputs, count)
 
         # J v: the defect rows, then the instance rows
         fin = self._jacprod_inputs(free, v, nodes, 'jvp')
@@ -1148,35 +1071,33 @@ class ConstraintCollocator(object):
     def _ensure_jacprod(self):
         """The product handle (built, checked and verified on first use; it
         borrows the problem handle's device data)."""
-        if getattr(self, '_jacprod', None) is not None:
-            return self._jacprod
-        hip = self._ensure_hip()
-        prog = self._build_jacprod_program()
-        hsaco, meta = self._build_jacprod_code_object()
-        handle = hb.HipJacobianProduct(hip, dict(
-            jvp_strips=meta['jvp_strips'], vjp_strips=meta['vjp_strips'],
-            num_tail=prog.r + prog.s, nnz_inst=len(prog.inst_jac_out)),
-            hsaco)
-        self._sync_known(hip, None)
-        try:
-            verdict = self._verify_jacprod(handle)
-        except hb.BuildRejected:
-            handle.release()
-            raise
-        self._jacprod_meta = dict(meta, hsaco=hsaco, verdict=verdict)
-        self._jacprod = handle
-        return handle
+        def create(hip):
+            prog = self._build_jacprod_program()
+            hsaco, meta = self._build_jacprod_code_object()
+            return hb.HipJacobianProduct(hip, dict(
+                jvp_strips=meta['jvp_strips'], vjp_strips=meta['vjp_strips'],
+                num_tail=prog.r + prog.s, nnz_inst=len(prog.inst_jac_out)),
+                hsaco), dict(meta, hsaco=hsaco)
+        return self._ensure_derived('_jacprod', create, self._verify_jacprod)
 
     def _generate_product(self, which):
         handle = self._ensure_jacprod()
-        hip = self._hip
         nfree, ncon = self.num_free, self.num_constraints
-        nin, nout = (nfree, ncon) if which == 'jvp' else (ncon, nfree)
-        launch = handle.jvp if which == 'jvp' else handle.vjp
-        name = 'v' if which == 'jvp' else 'w'
+        if which == 'jvp':
+            return self._derived_function(handle, handle.jvp, 'v', nfree,
+                                          ncon)
+        return self._derived_function(handle, handle.vjp, 'w', ncon, nfree)
+
+    def _derived_function(self, handle, launch, name, nin, nout):
+        """``f(free, vec) -> result`` over ``launch(free, vec, out, memory
+        kind)`` of a derived handle: host arrays in, a persistent page-locked
+        buffer of ``nout`` values out -- or torch CUDA tensors in, a new CUDA
+        tensor out; ``vec`` is called ``name`` and has ``nin`` values."""
+        hip = self._hip
+        nfree = self.num_free
         result = hb.pinned_empty(nout)
 
-        def product(free, vec):
+        def evaluate(free, vec):
             if hasattr(free, 'data_ptr'):
                 import torch
                 if tuple(free.shape) != (nfree,) or \
@@ -1203,8 +1124,8 @@ class ConstraintCollocator(object):
             self._sync_known(hip, free)
             launch(free, vec, result, hb.HOST)
             return result
-        product.handle = handle
-        return product
+        evaluate.handle = handle
+        return evaluate
 
     def generate_jvp_function(self):
         """Returns ``jvp(free, v) -> ndarray (num_constraints,)``: the

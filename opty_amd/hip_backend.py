@@ -1158,41 +1158,30 @@ class HipObjective(object):
         return value.value
 
 
-class HipHessian(object):
-    """One ``opty_hip_hessian`` handle: the exact Hessian of the constraint
-    Lagrangian of a :class:`HipProblem`, whose device data it borrows.  When
-    the problem's C handle is replaced (:meth:`HipProblem.reload`) or closed,
-    this handle is released first and created again for the new one on the
-    next call."""
+class _DerivedHandle(object):
+    """A C handle that borrows the device data of a :class:`HipProblem`.
+    When the problem's C handle is replaced (:meth:`HipProblem.reload`) or
+    closed, this handle is released first and created again for the new one
+    on the next call.  Subclasses name their ``_create`` / ``_destroy``
+    symbols and build their descriptor in ``_descriptor()``."""
 
-    def __init__(self, problem, desc, hsaco_path):
+    def __init__(self, problem, hsaco_path):
         self._lib = load_library()
         self._problem = problem
-        self._desc = dict(desc)
-        self._pattern = np.ascontiguousarray(desc['pattern'],
-                                             dtype=np.int32).reshape(-1)
-        self._irows = np.ascontiguousarray(desc['inst_rows'], dtype=np.int64)
-        self._icols = np.ascontiguousarray(desc['inst_cols'], dtype=np.int64)
         self._hsaco = hsaco_path
         self._h = None
         import weakref
         deps = problem.__dict__.setdefault('_dependents', weakref.WeakSet())
         deps.add(self)
         self._handle()
-        self.nnz = self._lib.opty_hip_hessian_nnz(self._h)
 
     def _handle(self):
         if self._h is None:
             if not getattr(self._problem, '_h', None):
                 raise HipBackendError('the problem handle is closed')
-            d = _HessDesc(PH=self._desc['PH'],
-                          nnz_inst=self._desc['nnz_inst'],
-                          strips=self._desc['strips'],
-                          pattern=_ptr(self._pattern),
-                          inst_rows=_ptr(self._irows),
-                          inst_cols=_ptr(self._icols))
+            d = self._descriptor()
             h = _P()
-            _check(self._lib.opty_hip_hessian_create(
+            _check(getattr(self._lib, self._create)(
                 self._problem._h, ctypes.byref(d), self._hsaco.encode(),
                 ctypes.byref(h)))
             self._h = h
@@ -1200,10 +1189,36 @@ class HipHessian(object):
 
     def release(self):
         if getattr(self, '_h', None):
-            self._lib.opty_hip_hessian_destroy(self._h)
+            getattr(self._lib, self._destroy)(self._h)
             self._h = None
 
     __del__ = release
+
+
+class HipHessian(_DerivedHandle):
+    """One ``opty_hip_hessian`` handle: the exact Hessian of the constraint
+    Lagrangian of a :class:`HipProblem`, whose device data it borrows.  When
+    the problem's C handle is replaced (:meth:`HipProblem.reload`) or closed,
+    this handle is released first and created again for the new one on the
+    next call."""
+
+    _create, _destroy = 'opty_hip_hessian_create', 'opty_hip_hessian_destroy'
+
+    def __init__(self, problem, desc, hsaco_path):
+        self._desc = dict(desc)
+        self._pattern = np.ascontiguousarray(desc['pattern'],
+                                             dtype=np.int32).reshape(-1)
+        self._irows = np.ascontiguousarray(desc['inst_rows'], dtype=np.int64)
+        self._icols = np.ascontiguousarray(desc['inst_cols'], dtype=np.int64)
+        super().__init__(problem, hsaco_path)
+        self.nnz = self._lib.opty_hip_hessian_nnz(self._h)
+
+    def _descriptor(self):
+        return _HessDesc(PH=self._desc['PH'], nnz_inst=self._desc['nnz_inst'],
+                         strips=self._desc['strips'],
+                         pattern=_ptr(self._pattern),
+                         inst_rows=_ptr(self._irows),
+                         inst_cols=_ptr(self._icols))
 
     def evaluate(self, free, lagrange, hess, mem):
         _check(self._lib.opty_hip_eval_hess(self._handle(), _ptr(free),
@@ -1214,41 +1229,20 @@ class HipHessian(object):
                                                   _ptr(cols), mem))
 
 
-class HipJacobianProduct(object):
+class HipJacobianProduct(_DerivedHandle):
     """One ``opty_hip_jacprod`` handle: ``J(free) v`` and ``J(free)^T w`` of a
     :class:`HipProblem`, whose device data it borrows.  When the problem's C
     handle is replaced (:meth:`HipProblem.reload`) or closed, this handle is
     released first and created again for the new one on the next call."""
 
+    _create, _destroy = 'opty_hip_jacprod_create', 'opty_hip_jacprod_destroy'
+
     def __init__(self, problem, desc, hsaco_path):
-        self._lib = load_library()
-        self._problem = problem
         self._desc = dict(desc)
-        self._hsaco = hsaco_path
-        self._h = None
-        import weakref
-        deps = problem.__dict__.setdefault('_dependents', weakref.WeakSet())
-        deps.add(self)
-        self._handle()
+        super().__init__(problem, hsaco_path)
 
-    def _handle(self):
-        if self._h is None:
-            if not getattr(self._problem, '_h', None):
-                raise HipBackendError('the problem handle is closed')
-            d = _JacprodDesc(**self._desc)
-            h = _P()
-            _check(self._lib.opty_hip_jacprod_create(
-                self._problem._h, ctypes.byref(d), self._hsaco.encode(),
-                ctypes.byref(h)))
-            self._h = h
-        return self._h
-
-    def release(self):
-        if getattr(self, '_h', None):
-            self._lib.opty_hip_jacprod_destroy(self._h)
-            self._h = None
-
-    __del__ = release
+    def _descriptor(self):
+        return _JacprodDesc(**self._desc)
 
     def jvp(self, free, v, out, mem):
         _check(self._lib.opty_hip_jacprod_jvp(self._handle(), _ptr(free),

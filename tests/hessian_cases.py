@@ -37,6 +37,11 @@ BLOCK_EDGE_CASES = ([('A', m) for m in EDGES] + [('E', m) for m in EDGES] +
                     [('C', m) for m in (1, 64, 65)] +
                     [(k, m) for k in 'BD' for m in (65, 129)])
 
+#: (label, N - 1) of tests/test_derived_handles_gpu.py: no instance constraint
+#: and a full block plus one node; instance constraints, an unknown parameter
+#: and a known trajectory (every kernel of both modules runs)
+LIFECYCLE_CASES = (('A', 65), ('C', 65))
+
 #: the code generator's default (``ConstraintCollocator._HESS_STRIP_OPS``)
 DEFAULT_VARIANT = (1500, False, 1)
 #: (label, (strip budget, forget, fast_trig)) of the emission paths that no
@@ -140,8 +145,9 @@ def prebuild_jobs():
     """Thunks that build the code objects of tests/test_hessian_kernel_gpu.py
     (``__graft_entry__.build`` runs them side by side): the Hessian module of
     every problem and forced variant, the constraint / Jacobian module of
-    every node count (its geometry depends on the launch size), and the
-    Hessian and product modules of the finite-difference check."""
+    every node count (its geometry depends on the launch size), the product
+    modules of the lifecycle cases, and the Hessian and product modules of
+    the finite-difference check."""
     import opty_amd
 
     def small():
@@ -154,6 +160,8 @@ def prebuild_jobs():
                 col._build_hessian_code_object()
         for label, variant in FORCED_VARIANTS:
             forced_module(collocator(label, 65), variant)
+        for label, ncn in LIFECYCLE_CASES:
+            collocator(label, ncn)._build_jacprod_code_object()
 
     def named(name):
         col = opty_amd.ConstraintCollocator(**problems.build(name))
