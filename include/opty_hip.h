@@ -172,10 +172,11 @@ typedef struct opty_hip_desc {
  * returns the one the library was built from.  A client built against another
  * version must not call the library: the descriptor grew in 5, 6, 7 and 8
  * (8: the restricted kernels' geometry, opty_hip_output_*; 9: the
- * opty_hip_jacprod_* entry points), and
+ * opty_hip_jacprod_* entry points; 10: the opty_hip_objhess_* entry points),
+ * and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
-#define OPTY_HIP_ABI_VERSION 9
+#define OPTY_HIP_ABI_VERSION 10
 int opty_hip_abi_version(void);
 
 /* (The build verification's device side -- register poisoner, instruction
@@ -500,6 +501,63 @@ int opty_hip_objective_set_stream(opty_hip_objective *o, void *hip_stream);
  * memory or NULL for the value alone; free: (n+q)*N + r doubles in `mem`. */
 int opty_hip_objective_eval(opty_hip_objective *o, const double *free,
                             double *value, double *grad, int32_t mem);
+
+/* ---- exact Hessian of the objective -----------------------------------------
+ * H = d2 f / d free^2 of the value f that opty_hip_objective_eval returns,
+ * for the objectives it supports, sum_j a_j(p) Integral(g_j, t) + b(p) with
+ * G = sum_j a_j g_j:
+ *   backward Euler: f = h sum_{i=1}^{N-1} G(z_i, p) + b(p)  (H is then also the
+ *                   Jacobian of the gradient opty_hip_objective_eval returns)
+ *   midpoint:       f = h sum_{i=0}^{N-2} G((z_i + z_{i+1})/2, p) + b(p)  (the
+ *                   reference-shaped midpoint gradient evaluates its trajectory
+ *                   part at the node values and is not the gradient of f: H is
+ *                   the Hessian of the VALUE)
+ * Contract of the constraint Hessian below: lower triangle (row >= col on the
+ * GLOBAL free indices), triplets, a (row, col) pair may repeat and the matrix
+ * is the SUM of its triplets.  Both methods have N-1 quadrature points; point
+ * j is node j + base (base = 1 backward Euler, 0 midpoint).
+ *   out : out[e*(N-1) + j] for per-point entry e < E and point j, then the T
+ *         parameter-parameter entries out[E*(N-1) + t] = h sum_j G_pp + b_pp;
+ *         every value times obj_factor.  nnz = E*(N-1) + T may be 0.
+ * The code object exports `opty_objhess` (lane = quadrature point) and, when
+ * T > 0, `opty_objhess_fin` (one wave: block partials added in a fixed
+ * order).  No atomics: every value is written exactly once per call and the
+ * same inputs give the same bits.  Nothing is launched when nnz == 0. */
+typedef struct opty_hip_objhess opty_hip_objhess;
+
+typedef struct opty_hip_objhess_desc {
+    int64_t N;        /* collocation nodes                                   */
+    int32_t n, q, r;  /* states, unknown inputs, unknown parameters          */
+    int32_t device;   /* HIP device ordinal                                  */
+    double h;         /* node time interval                                  */
+    int32_t base;     /* node of quadrature point 0: 1 backward Euler, 0 mid */
+    int32_t E;        /* per-point entries                                   */
+    int32_t T;        /* parameter-parameter entries                         */
+} opty_hip_objhess_desc;
+
+/* pattern (host memory, copied): 4 int32 per per-point entry e, (row_var,
+ * row_off, col_var, col_off) -- global index of a side = var*N + j + base +
+ * off for var >= 0 (off 0, or 1 with base 0), (n+q)*N + off for var == -1
+ * (parameter off) -- then 2 int32 per parameter-parameter entry, the
+ * parameters (a, b) of its row and column.  May be null when E == T == 0. */
+int opty_hip_objhess_create(const opty_hip_objhess_desc *desc,
+                            const int32_t *pattern,
+                            const char *code_object_path,
+                            opty_hip_objhess **out);
+int opty_hip_objhess_destroy(opty_hip_objhess *o);
+int opty_hip_objhess_set_stream(opty_hip_objhess *o, void *hip_stream);
+/* E*(N-1) + T */
+int64_t opty_hip_objhess_nnz(const opty_hip_objhess *o);
+/* int64 row / column indices of every value, same order, in `mem` memory. */
+int opty_hip_objhess_indices(opty_hip_objhess *o, int64_t *rows,
+                             int64_t *cols, int32_t mem);
+/* free: (n+q)*N + r doubles, out: nnz doubles, both in `mem` memory.
+ * Synchronous for OPTY_HIP_HOST (staged through buffers of the handle);
+ * OPTY_HIP_DEVICE writes straight to `out` -- which may point into a larger
+ * buffer, a double's alignment is enough -- and is enqueued on the handle's
+ * stream. */
+int opty_hip_objhess_eval(opty_hip_objhess *o, const double *free,
+                          double obj_factor, double *out, int32_t mem);
 
 /* ---- plain matrix functions: the reference's plugin call shape ---------------
  * `f = ufuncify_matrix(args, expr, const=...)`, `f(result, *num_args)`

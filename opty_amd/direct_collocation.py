@@ -3005,9 +3005,32 @@ class Problem(object):
         def hessianstructure():
             return structure
 
+        # a device-backed ``values`` (``create_objective_hessian_function``)
+        # applies ``obj_factor`` itself and can fill a device buffer in place
+        on_device = isinstance(getattr(values, 'handle', None),
+                               hb.HipObjectiveHessian)
+
         def hessian(free, lagrange, obj_factor):
+            if hasattr(free, 'data_ptr'):
+                if not on_device:
+                    raise TypeError(
+                        'Problem.hessian with torch CUDA tensors needs an '
+                        'obj_hessian whose values have a device handle '
+                        '(values.handle: opty_amd.create_objective_hessian_'
+                        'function); a hand-written values callable works on '
+                        'host arrays only.')
+                import torch
+                chess = con_hess(free, lagrange)
+                out = torch.empty(num_con + len(rows), dtype=torch.float64,
+                                  device=chess.device)
+                out[:num_con] = chess
+                values(free, obj_factor, out[num_con:])
+                return out
             out = np.empty(num_con + len(rows))
             out[:num_con] = con_hess(free, lagrange)
+            if on_device:
+                values(free, obj_factor, out[num_con:])
+                return out
             v = values(self, free) if nargs == 2 else values(free)
             out[num_con:] = obj_factor*np.asarray(v, dtype=float)
             return out

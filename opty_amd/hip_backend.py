@@ -29,7 +29,7 @@ DEFAULT_CACHE = os.path.join(_PKG, '_cache')
 ARCH = 'gfx950'
 
 #: OPTY_HIP_ABI_VERSION of include/opty_hip.h these bindings were written for
-ABI_VERSION = 9
+ABI_VERSION = 10
 HOST, DEVICE = 0, 1
 #: hipStreamLegacy: the null / legacy default stream (torch's default)
 STREAM_LEGACY = 1
@@ -407,6 +407,14 @@ class _ObjDesc(ctypes.Structure):
                 ('device', ctypes.c_int32), ('h', ctypes.c_double)]
 
 
+class _ObjHessDesc(ctypes.Structure):
+    _fields_ = [('N', ctypes.c_int64), ('n', ctypes.c_int32),
+                ('q', ctypes.c_int32), ('r', ctypes.c_int32),
+                ('device', ctypes.c_int32), ('h', ctypes.c_double),
+                ('base', ctypes.c_int32), ('E', ctypes.c_int32),
+                ('T', ctypes.c_int32)]
+
+
 _lib = None
 
 #: every symbol ``include/opty_hip.h`` declares: (restype, argtypes)
@@ -485,6 +493,15 @@ _SIGNATURES = {
     'opty_hip_objective_set_stream': (ctypes.c_int, [_P, _P]),
     'opty_hip_objective_eval': (ctypes.c_int, [_P, _P, _P, _P,
                                                ctypes.c_int32]),
+    'opty_hip_objhess_create': (ctypes.c_int, [ctypes.POINTER(_ObjHessDesc),
+                                               _P, ctypes.c_char_p,
+                                               ctypes.POINTER(_P)]),
+    'opty_hip_objhess_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_objhess_set_stream': (ctypes.c_int, [_P, _P]),
+    'opty_hip_objhess_nnz': (ctypes.c_int64, [_P]),
+    'opty_hip_objhess_indices': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32]),
+    'opty_hip_objhess_eval': (ctypes.c_int, [_P, _P, ctypes.c_double, _P,
+                                             ctypes.c_int32]),
     'opty_hip_host_alloc': (ctypes.c_void_p, [ctypes.c_size_t]),
     'opty_hip_host_free': (ctypes.c_int, [_P]),
     'opty_hip_device_alloc': (ctypes.c_void_p, [ctypes.c_int32,
@@ -1156,6 +1173,55 @@ class HipObjective(object):
         _check(self._lib.opty_hip_objective_eval(
             self._h, _ptr(free), ctypes.addressof(value), _ptr(grad), mem))
         return value.value
+
+
+class HipObjectiveHessian(object):
+    """One ``opty_hip_objhess`` handle: the exact Hessian of the objective
+    (lower triangle, triplets; ``include/opty_hip.h``).  ``pattern``: ``(row
+    var, row off, col var, col off)`` per per-point entry, ``tail_pairs``:
+    the parameters ``(a, b)`` per parameter-parameter entry."""
+
+    def __init__(self, desc, pattern, tail_pairs, hsaco_path):
+        self._lib = load_library()
+        if self._lib.opty_hip_device_count() == 0:
+            raise HipBackendError('no HIP device is visible: the HIP '
+                                  'backend has no CPU fallback')
+        self._h = _P()
+        table = np.ascontiguousarray(np.concatenate((
+            np.asarray(pattern, dtype=np.int32).reshape(-1),
+            np.asarray(tail_pairs, dtype=np.int32).reshape(-1))))
+        assert len(table) == 4*desc['E'] + 2*desc['T']
+        d = _ObjHessDesc(**desc)
+        _check(self._lib.opty_hip_objhess_create(
+            ctypes.byref(d), _ptr(table) if len(table) else None,
+            hsaco_path.encode(), ctypes.byref(self._h)))
+        self.desc = dict(desc)
+        self.nnz = self._lib.opty_hip_objhess_nnz(self._h)
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.opty_hip_objhess_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_stream(self, stream_ptr):
+        _check(self._lib.opty_hip_objhess_set_stream(self._h, stream_ptr))
+
+    def use_torch_stream(self, stream=None):
+        """Run this handle's work on a torch stream (default: the current
+        one), ordered with the torch operations issued there."""
+        self.set_stream(torch_stream_pointer(stream))
+
+    def indices(self, rows, cols, mem):
+        _check(self._lib.opty_hip_objhess_indices(self._h, _ptr(rows),
+                                                  _ptr(cols), mem))
+
+    def evaluate(self, free, obj_factor, out, mem):
+        """Fills ``out`` (``nnz`` values) with ``obj_factor`` times the
+        Hessian's values; enqueued on the handle's stream for ``DEVICE``."""
+        _check(self._lib.opty_hip_objhess_eval(
+            self._h, _ptr(free), float(obj_factor), _ptr(out), mem))
 
 
 class _DerivedHandle(object):
