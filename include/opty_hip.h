@@ -172,11 +172,11 @@ typedef struct opty_hip_desc {
  * returns the one the library was built from.  A client built against another
  * version must not call the library: the descriptor grew in 5, 6, 7 and 8
  * (8: the restricted kernels' geometry, opty_hip_output_*; 9: the
- * opty_hip_jacprod_* entry points; 10: the opty_hip_objhess_* entry points),
- * and
+ * opty_hip_jacprod_* entry points; 10: the opty_hip_objhess_* entry points;
+ * 11: the opty_hip_hessmv_* entry points), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
-#define OPTY_HIP_ABI_VERSION 10
+#define OPTY_HIP_ABI_VERSION 11
 int opty_hip_abi_version(void);
 
 /* (The build verification's device side -- register poisoner, instruction
@@ -752,6 +752,73 @@ int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free,
                          const double *v, double *out, int32_t mem);
 int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free,
                          const double *w, double *out, int32_t mem);
+
+/* ---- Hessian operator: y = H v from the stored triplets ----------------------
+ * H is the symmetric matrix whose LOWER triangle is the SUM of the triplets of
+ * the Hessian of the Lagrangian: a triplet (r, c, a) adds a*v[c] to y[r] and,
+ * when r != c, a*v[r] to y[c]; a diagonal triplet counts once.  `values` is
+ * laid out as its pieces are evaluated, in this order:
+ *   node section       values[i*PH + e], constraint node i (opty_hip_eval_hess;
+ *                      `pattern` as in opty_hip_hessian_desc)
+ *   instance entries   nnz_inst values, explicit (inst_rows, inst_cols)
+ *   objective section  values[.. + e*(N-1) + j], quadrature point j
+ *                      (opty_hip_objhess_eval; `obj_pattern`: (var_a, off_a,
+ *                      var_b, off_b) per entry, free index var*N + j + obj_base
+ *                      + off, or the tail entry (n+q)*N + off for var == -1);
+ *                      E = T = 0: no objective section
+ *   parameter-parameter entries   T values, explicit (tail_rows, tail_cols)
+ * Relative to a node every side of an entry of either section is (row, slot),
+ * slot in {0, 1}, or a tail entry; anything else is refused at creation, as
+ * are explicit indices outside [0, num_free) or above the diagonal.
+ *
+ * One kernel family of this library serves every problem (no code object):
+ * `opty_hessmv` (lane = node; blocks of 64 lanes that advance by 63 nodes; an
+ * LDS accumulator per distinct side and lane) and `opty_hessmv_fin` (one wave:
+ * the tail entries from the block partials, in block order, then the explicit
+ * triplets in stored order by one lane; launched only when the problem has
+ * tail entries or explicit triplets).  Every element of y is stored exactly
+ * once by opty_hessmv or by opty_hessmv_fin's last loop -- rows that no triplet
+ * touches get 0.0 --, in a fixed order of operations and without atomics: the
+ * same inputs give the same bits in every call and for both memory kinds.
+ * The distinct sides must fit the LDS of one block (1 KiB per side next to a
+ * 16.5 KiB tile); a pattern with more is refused at creation with a message
+ * that names the count and the limit.
+ *
+ * The handle BORROWS its problem handle for N, n, q, r, s, device and stream
+ * (it reads none of the problem's tables) and must be destroyed before it. */
+typedef struct opty_hip_hessmv opty_hip_hessmv;
+
+typedef struct opty_hip_hessmv_desc {
+    int32_t PH;        /* stored entries per constraint node                   */
+    int32_t nnz_inst;  /* entries of the instance constraints                  */
+    int32_t E;         /* objective entries per quadrature point               */
+    int32_t obj_base;  /* 1: backward Euler, 0: midpoint                       */
+    int32_t T;         /* parameter-parameter entries of the objective         */
+    const int32_t *pattern;      /* 4*PH   (host memory, as all tables here)   */
+    const int64_t *inst_rows;    /* nnz_inst global indices each               */
+    const int64_t *inst_cols;
+    const int32_t *obj_pattern;  /* 4*E                                        */
+    const int64_t *tail_rows;    /* T global indices each                      */
+    const int64_t *tail_cols;
+} opty_hip_hessmv_desc;
+
+int opty_hip_hessmv_create(opty_hip_problem *p,
+                           const opty_hip_hessmv_desc *desc,
+                           opty_hip_hessmv **out);
+int opty_hip_hessmv_destroy(opty_hip_hessmv *h);
+/* PH*(N-1) + nnz_inst + E*(N-1) + T */
+int64_t opty_hip_hessmv_nnz(const opty_hip_hessmv *h);
+/* The side table: returns the number of distinct sides, stores the number of
+ * trajectory sides (they come first, ascending (row, slot); the tail sides
+ * follow, ascending offset) and up to `room` (row, slot) pairs -- (-1, offset)
+ * for a tail side.  `sides` and `num_trajectory` may be NULL. */
+int32_t opty_hip_hessmv_sides(const opty_hip_hessmv *h, int32_t *sides,
+                              int32_t room, int32_t *num_trajectory);
+/* values: hessmv_nnz doubles (8-byte alignment is enough), v and y: num_free
+ * doubles, all in `mem` memory; y must not overlap v or values.  Synchronous
+ * for OPTY_HIP_HOST, enqueued on the problem's stream for OPTY_HIP_DEVICE. */
+int opty_hip_hessmv_apply(opty_hip_hessmv *h, const double *values,
+                          const double *v, double *y, int32_t mem);
 
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);

@@ -516,6 +516,92 @@ def assemble_vjp(prog, N, adj, inst, w, atom_free_index):
     return out
 
 
+def hessian_side_table(pattern, obj_pattern=(), obj_base=0):
+    """The side slots of a Hessian product (``opty_hessmv``): relative to a
+    node every side of an entry of the node section (``pattern``,
+    :meth:`HessianProgram.index_pattern`) and of the objective section
+    (``obj_pattern``, slot = ``obj_base`` + offset) is ``(row, slot)`` with
+    ``slot`` in {0, 1} -- free index ``row*N + i + slot`` -- or a tail entry
+    ``(-1, offset)``.  Returns ``(sides, num_trajectory, entries,
+    obj_entries)``: the distinct sides, trajectory sides first in ascending
+    ``(row, slot)`` order, then the tail sides by offset; ``entries[e] = (slot
+    of side a, slot of side b)`` per node entry, ``obj_entries`` the same per
+    objective entry."""
+    def sides_of(pat, base):
+        out = []
+        for ra, oa, rb, ob in [tuple(int(x) for x in e) for e in pat]:
+            pair = []
+            for row, off in ((ra, oa), (rb, ob)):
+                side = (row, base + off) if row >= 0 else (-1, off)
+                if row < -1 or (row >= 0 and side[1] not in (0, 1)) or \
+                        (row < 0 and off < 0):
+                    raise ValueError('side (%d, %d) is neither (row, slot in '
+                                     '{0, 1}) nor a tail entry' % side)
+                pair.append(side)
+            out.append(tuple(pair))
+        return out
+    node, obj = sides_of(pattern, 0), sides_of(obj_pattern, int(obj_base))
+    distinct = {side for pair in node + obj for side in pair}
+    sides = sorted(distinct, key=_side_order)
+    slot = {side: k for k, side in enumerate(sides)}
+    return (sides, sum(1 for row, _ in sides if row >= 0),
+            [(slot[a], slot[b]) for a, b in node],
+            [(slot[a], slot[b]) for a, b in obj])
+
+
+def assemble_hessmv(N, num_rows, num_tail, values, v, pattern, inst_rows=(),
+                    inst_cols=(), obj_pattern=(), obj_base=0, tail_rows=(),
+                    tail_cols=()):
+    """``y = H v`` from the stored triplets, ``H`` the symmetric matrix whose
+    lower triangle is the sum of the triplets; ``values`` laid out ``[node
+    section (i*PH + e) | instance entries | objective section (e*(N-1) + j) |
+    parameter-parameter entries]``, ``num_rows = n + q`` trajectory rows and
+    ``num_tail`` tail entries of ``free``.  The host statement of
+    ``opty_hessmv`` / ``opty_hessmv_fin``: per side slot ``S`` the sum over
+    the entries of node ``i`` of ``value * v[other side]`` (a diagonal entry
+    once), then ``y[R*N + p] = S_R0(p) + S_R1(p - 1)`` with the missing term
+    dropped at both ends, a tail entry the sum over all nodes, and last the
+    explicit triplets in stored order."""
+    import numpy as np
+    N, ncn = int(N), int(N) - 1
+    sides, ntraj, entries, obj_entries = hessian_side_table(
+        pattern, obj_pattern, obj_base)
+    PH, E = len(entries), len(obj_entries)
+    ni, nt = len(inst_rows), len(tail_rows)
+    values = np.asarray(values, dtype=float)
+    v = np.asarray(v, dtype=float)
+    tail = num_rows*N
+    assert values.shape == ((PH + E)*ncn + ni + nt,)
+    assert v.shape == (tail + num_tail,)
+    node = values[:PH*ncn].reshape(ncn, PH)
+    inst = values[PH*ncn:PH*ncn + ni]
+    obj = values[PH*ncn + ni:PH*ncn + ni + E*ncn].reshape(E, ncn)
+    par = values[PH*ncn + ni + E*ncn:]
+    i = np.arange(ncn)
+    at = [np.broadcast_to(v[row*N + i + off] if row >= 0 else v[tail + off],
+                          (ncn,)) for row, off in sides]
+    S = np.zeros((len(sides), ncn))
+    for val, table in ((node.T, entries), (obj, obj_entries)):
+        for e, (a, b) in enumerate(table):
+            S[a] += val[e]*at[b]
+            if a != b:
+                S[b] += val[e]*at[a]
+    y = np.zeros(tail + num_tail)
+    for k, (row, off) in enumerate(sides):
+        if row >= 0:
+            # slot 0: p = i; slot 1: p = i + 1
+            y[row*N + off:row*N + off + ncn] += S[k]
+        else:
+            y[tail + off] += S[k].sum()
+    for rows, cols, val in ((inst_rows, inst_cols, inst),
+                            (tail_rows, tail_cols, par)):
+        for r, c, a in zip(rows, cols, val):
+            y[r] += a*v[c]
+            if r != c:
+                y[c] += a*v[r]
+    return y
+
+
 def matrix_program(dag, outputs, num_vec, num_const, shape):
     """Program of a plain matrix of expressions (the reference's
     ``ufuncify_matrix`` call shape, ``opty/utils.py:639-640``): ``outputs`` are

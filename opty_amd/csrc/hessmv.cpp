@@ -1,0 +1,479 @@
+// hessmv.cpp -- the Hessian-product handle of libopty_hip.so: y = H v from the
+// stored triplets of the Hessian of the Lagrangian (include/opty_hip.h,
+// "Hessian operator").  H is the symmetric matrix whose lower triangle is the
+// SUM of the triplets; the value vector is laid out as Problem.hessian returns
+// it: [node section | instance entries | objective section | parameter-
+// parameter entries].
+//
+// The handle borrows its problem handle for N, n, q, r, s, device and stream.
+// It loads no code object: the two kernels below are part of this library and
+// serve every problem.  Both node-indexed sections have closed-form indices:
+// relative to node i every side of an entry is (row, slot) -- free index
+// row*N + i + slot, slot in {0, 1} -- or a tail entry.  The distinct sides get
+// one slot each in a small table (trajectory sides first, then tail sides);
+// opty_hessmv walks the entries once per block and adds value * v[other side]
+// into the lane's column of an LDS accumulator acc[side][lane].
+//
+//   y[R*N + p]  = S_R0(node p) + S_R1(node p - 1)      (trajectory row R)
+//   y[tail + j] = sum over all nodes of S_tail_j       (parameter / h)
+//
+// Blocks of 64 lanes advance by 63 nodes (opty_vjp's scheme): lane l of block
+// b is node 63 b + l, lane l >= 1 writes p = 63 b + l from its own S_R0 and
+// lane l - 1's S_R1, read from LDS; lane 0 of block 0 writes p = 0.  Lane 0 of
+// a later block repeats the previous block's last node and counts as zero in
+// the tail sums.  Every element of y is stored once; no atomics.
+#include "opty_internal.h"
+
+#include <cstdint>
+#include <map>
+
+using namespace opty;
+
+namespace {
+
+constexpr long long kStride = 63;   // nodes a block advances by
+constexpr int kChunk = 32;          // entries of a node per LDS tile
+// odd pitch in doubles: the 32 lanes of a half wave that read one column of
+// the tile with 8-byte reads hit 32 distinct pairs of the 64 banks
+constexpr int kPitch = kChunk + 1;
+constexpr size_t kTileBytes = (size_t)64*kPitch*sizeof(double);
+
+struct MvArgs {
+    const double *val;      // node section, val[i*PH + e]
+    const double *oval;     // objective section, oval[e*ncn + j]
+    const double *v;
+    double *y;
+    double *part;           // part[b*nT + t]
+    const int *ent;         // (side a, side b) per node entry
+    const int *oent;        // ... per objective entry
+    const int *sides;       // (row, slot) per side; row -1: (-1, tail offset)
+    const int *rowside;     // side of (R, 0) and (R, 1) per trajectory row, or -1
+    long long N;
+    int PH, E, nS, nT, nrows;
+};
+
+// lane = constraint node (= quadrature point); one wave per block
+__global__ void __launch_bounds__(64)
+opty_hessmv(MvArgs a) {
+    extern __shared__ double lds[];
+    const int lane = threadIdx.x;
+    const int nA = a.nS + a.nT;
+    double *tile = lds;                       // [64][kPitch]
+    double *vs = lds + 64*kPitch;             // [nA][64]
+    double *acc = vs + (size_t)nA*64;         // [nA][64]
+    const long long N = a.N, ncn = N - 1;
+    const long long i0 = (long long)blockIdx.x*kStride;
+    const long long i = i0 + lane;
+    const bool valid = i < ncn;
+    const long long tail = (long long)a.nrows*N;
+    // nodes of this block that exist (>= 1: i0 < ncn for every block)
+    const int nv = (int)(ncn - i0 < 64 ? ncn - i0 : 64);
+
+    // v at every side (a coalesced row load; tail sides broadcast), zero
+    // accumulators.  i < ncn: row*N + i + slot <= row*N + N - 1.
+    for (int s = 0; s < nA; ++s) {
+        const int row = a.sides[2*s], off = a.sides[2*s + 1];
+        double x = 0.0;
+        if (valid) x = row >= 0 ? a.v[(long long)row*N + i + off]
+                                : a.v[tail + off];
+        vs[s*64 + lane] = x;
+        acc[s*64 + lane] = 0.0;
+    }
+
+    // node section: the block's nv*PH values are contiguous; a chunk is kChunk
+    // entries of every node, loaded as rows of w consecutive doubles (two
+    // nodes per wave instruction), read back lane = node
+    const double *blk = a.val + i0*a.PH;
+    const int half = lane >> 5, col = lane & 31;
+    for (int c0 = 0; c0 < a.PH; c0 += kChunk) {
+        const int w = a.PH - c0 < kChunk ? a.PH - c0 : kChunk;
+        __syncthreads();
+        if (col < w)
+            for (int nd = half; nd < nv; nd += 2)
+                tile[nd*kPitch + col] = blk[(long long)nd*a.PH + c0 + col];
+        __syncthreads();
+        for (int k = 0; k < w; ++k) {
+            const int sa = a.ent[2*(c0 + k)], sb = a.ent[2*(c0 + k) + 1];
+            const double x = valid ? tile[lane*kPitch + k] : 0.0;
+            acc[sa*64 + lane] += x*vs[sb*64 + lane];
+            if (sa != sb) acc[sb*64 + lane] += x*vs[sa*64 + lane];
+        }
+    }
+
+    // objective section: entry-major, lane = point, coalesced as it is
+    for (int e = 0; e < a.E; ++e) {
+        const int sa = a.oent[2*e], sb = a.oent[2*e + 1];
+        const double x = valid ? a.oval[(long long)e*ncn + i] : 0.0;
+        acc[sa*64 + lane] += x*vs[sb*64 + lane];
+        if (sa != sb) acc[sb*64 + lane] += x*vs[sa*64 + lane];
+    }
+    __syncthreads();
+
+    // trajectory rows: p = i; S_R0 of this lane + S_R1 of the lane before
+    const bool writes = (lane > 0 || blockIdx.x == 0) && i <= ncn;
+    for (int R = 0; R < a.nrows; ++R) {
+        const int s0 = a.rowside[2*R], s1 = a.rowside[2*R + 1];
+        double x = 0.0;
+        if (s0 >= 0) x = acc[s0*64 + lane];
+        if (s1 >= 0 && lane > 0) x += acc[s1*64 + lane - 1];
+        if (writes) a.y[(long long)R*N + i] = x;
+    }
+
+    // tail sides: a fixed tree over the lanes; the repeated node counts once
+    for (int t = 0; t < a.nT; ++t) {
+        double x = acc[(a.nS + t)*64 + lane];
+        if (lane == 0 && blockIdx.x > 0) x = 0.0;
+        for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d);
+        if (lane == 0) a.part[(long long)blockIdx.x*a.nT + t] = x;
+    }
+}
+
+struct FinArgs {
+    const double *part;
+    const double *ival;     // instance values, then (pval) parameter-parameter
+    const double *pval;
+    const double *v;
+    double *y;
+    const int *sides;
+    const long long *irows, *icols, *prows, *pcols;
+    long long nblk, tail;
+    int nS, nT, ntail, nnz_inst, T;
+};
+
+// One wave, enqueued behind opty_hessmv: the tail entries of y (block
+// partials added in block order; an entry without a side is 0.0), then one
+// lane applies the explicit triplets in stored order -- to the tail entries
+// in LDS, to trajectory entries (which opty_hessmv stored) in place.
+__global__ void __launch_bounds__(64)
+opty_hessmv_fin(FinArgs a) {
+    extern __shared__ double tl[];          // [ntail]
+    const int lane = threadIdx.x;
+    for (int j = lane; j < a.ntail; j += 64) tl[j] = 0.0;
+    __syncthreads();
+    for (int t = lane; t < a.nT; t += 64) {
+        double x = 0.0;
+        for (long long b = 0; b < a.nblk; ++b) x += a.part[b*a.nT + t];
+        tl[a.sides[2*(a.nS + t) + 1]] = x;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        auto add = [&](long long at, double x) {
+            if (at >= a.tail) tl[at - a.tail] += x;
+            else a.y[at] += x;
+        };
+        auto apply = [&](long long r, long long c, double x) {
+            add(r, x*a.v[c]);
+            if (r != c) add(c, x*a.v[r]);
+        };
+        for (int k = 0; k < a.nnz_inst; ++k)
+            apply(a.irows[k], a.icols[k], a.ival[k]);
+        for (int k = 0; k < a.T; ++k)
+            apply(a.prows[k], a.pcols[k], a.pval[k]);
+    }
+    __syncthreads();
+    for (int j = lane; j < a.ntail; j += 64) a.y[a.tail + j] = tl[j];
+}
+
+}  // namespace
+
+struct opty_hip_hessmv : Borrowed {
+    opty_hip_hessmv_desc d{};
+    std::vector<int> sides;     // (row, slot) per side, trajectory sides first
+    int nS = 0, nT = 0;
+    size_t lds_main = 0, lds_fin = 0;
+    int *d_ent = nullptr, *d_oent = nullptr, *d_sides = nullptr,
+        *d_rowside = nullptr;
+    long long *d_irows = nullptr, *d_icols = nullptr, *d_prows = nullptr,
+              *d_pcols = nullptr;
+    double *d_part = nullptr;
+    // staging for host callers
+    double *d_val = nullptr, *d_v = nullptr, *d_y = nullptr;
+    long long ncn() const { return p->d.N - 1; }
+    long long blocks() const { return (ncn() + kStride - 1)/kStride; }
+    int nrows() const { return p->d.n + p->d.q; }
+    int ntail() const { return p->d.r + p->d.s; }
+    int64_t nnz() const {
+        return (int64_t)(d.PH + d.E)*ncn() + d.nnz_inst + d.T;
+    }
+};
+
+namespace {
+
+int check_pattern(const char *what, const int32_t *pat, int count, int base,
+                  int nrows, int ntail) {
+    for (int e = 0; e < count; ++e)
+        for (int k = 0; k < 2; ++k) {
+            const int row = pat[4*e + 2*k], off = pat[4*e + 2*k + 1];
+            if (row < -1 || row >= nrows)
+                return fail("%s entry %d: row %d outside [-1, %d)", what, e,
+                            row, nrows);
+            if (row >= 0 && (base + off < 0 || base + off > 1))
+                return fail("%s entry %d: slot %d outside {0, 1}", what, e,
+                            base + off);
+            if (row < 0 && (off < 0 || off >= ntail))
+                return fail("%s entry %d: tail offset %d outside [0, %d)",
+                            what, e, off, ntail);
+        }
+    return 0;
+}
+
+int check_explicit(const char *what, const int64_t *rows, const int64_t *cols,
+                   int count, int64_t num_free) {
+    for (int k = 0; k < count; ++k) {
+        if (rows[k] < 0 || rows[k] >= num_free || cols[k] < 0 ||
+            cols[k] >= num_free)
+            return fail("%s entry %d: (%lld, %lld) outside [0, %lld)", what,
+                        k, (long long)rows[k], (long long)cols[k],
+                        (long long)num_free);
+        if (rows[k] < cols[k])
+            return fail("%s entry %d: (%lld, %lld) is above the diagonal "
+                        "(row < col)", what, k, (long long)rows[k],
+                        (long long)cols[k]);
+    }
+    return 0;
+}
+
+template <typename T>
+int upload(T **dev, const T *host, size_t count) {
+    if (!count) return 0;
+    HIP_TRY(hipMalloc((void **)dev, count*sizeof(T)));
+    HIP_TRY(hipMemcpy(*dev, host, count*sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int opty_hip_hessmv_create(opty_hip_problem *p,
+                           const opty_hip_hessmv_desc *desc,
+                           opty_hip_hessmv **out) {
+    if (!p || !desc || !out) return fail("null argument");
+    if (desc->PH < 0 || desc->nnz_inst < 0 || desc->E < 0 || desc->T < 0)
+        return fail("bad Hessian-product descriptor (PH %d, nnz_inst %d, E "
+                    "%d, T %d)", desc->PH, desc->nnz_inst, desc->E, desc->T);
+    if (desc->PH > 0 && !desc->pattern) return fail("null index pattern");
+    if (desc->E > 0 && !desc->obj_pattern)
+        return fail("null objective index pattern");
+    if (desc->nnz_inst > 0 && (!desc->inst_rows || !desc->inst_cols))
+        return fail("null instance indices");
+    if (desc->T > 0 && (!desc->tail_rows || !desc->tail_cols))
+        return fail("null parameter-parameter indices");
+    if (desc->E > 0 && desc->obj_base != 0 && desc->obj_base != 1)
+        return fail("obj_base %d outside {0, 1}", desc->obj_base);
+    if (p->d.N < 2) return fail("N %lld < 2", (long long)p->d.N);
+    const int nrows = p->d.n + p->d.q, ntail = p->d.r + p->d.s;
+    if (int rc = check_pattern("pattern", desc->pattern, desc->PH, 0, nrows,
+                               ntail))
+        return rc;
+    if (int rc = check_pattern("objective pattern", desc->obj_pattern,
+                               desc->E, desc->obj_base, nrows, ntail))
+        return rc;
+    if (int rc = check_explicit("instance", desc->inst_rows, desc->inst_cols,
+                                desc->nnz_inst, p->num_free()))
+        return rc;
+    if (int rc = check_explicit("parameter-parameter", desc->tail_rows,
+                                desc->tail_cols, desc->T, p->num_free()))
+        return rc;
+
+    // the side table: distinct (row, slot) in ascending order, then the tail
+    // offsets in ascending order (hessian_side_table of codegen/program.py)
+    std::map<std::pair<int, int>, int> traj, tails;
+    auto note = [&](const int32_t *pat, int count, int base) {
+        for (int e = 0; e < count; ++e)
+            for (int k = 0; k < 2; ++k) {
+                const int row = pat[4*e + 2*k], off = pat[4*e + 2*k + 1];
+                if (row >= 0) traj[{row, base + off}] = 0;
+                else tails[{-1, off}] = 0;
+            }
+    };
+    note(desc->pattern, desc->PH, 0);
+    note(desc->obj_pattern, desc->E, desc->obj_base);
+    std::vector<int> sides;
+    for (auto *m : {&traj, &tails})
+        for (auto &kv : *m) {
+            kv.second = (int)sides.size()/2;
+            sides.push_back(kv.first.first);
+            sides.push_back(kv.first.second);
+        }
+    const int nS = (int)traj.size(), nT = (int)tails.size();
+    auto slots = [&](const int32_t *pat, int count, int base) {
+        std::vector<int> ent(2*(size_t)count);
+        for (int e = 0; e < count; ++e)
+            for (int k = 0; k < 2; ++k) {
+                const int row = pat[4*e + 2*k], off = pat[4*e + 2*k + 1];
+                ent[2*e + k] = row >= 0 ? traj[{row, base + off}]
+                                        : tails[{-1, off}];
+            }
+        return ent;
+    };
+    const std::vector<int> ent = slots(desc->pattern, desc->PH, 0),
+                           oent = slots(desc->obj_pattern, desc->E,
+                                        desc->obj_base);
+    std::vector<int> rowside(2*(size_t)nrows, -1);
+    for (auto &kv : traj) rowside[2*kv.first.first + kv.first.second] =
+        kv.second;
+
+    if (int rc = use_device(p)) return rc;
+    // LDS: the tile, v and the accumulator per side and lane
+    int limit = 0;
+    HIP_TRY(hipDeviceGetAttribute(&limit,
+                                  hipDeviceAttributeMaxSharedMemoryPerBlock,
+                                  p->d.device));
+    const size_t lds_main = kTileBytes + (size_t)(nS + nT)*2*64*sizeof(double);
+    const size_t lds_fin = (size_t)std::max(1, ntail)*sizeof(double);
+    if (lds_main > (size_t)limit)
+        return fail("%d sides (%d trajectory, %d tail) need %zu bytes of LDS "
+                    "per block, the limit is %d bytes (%d sides)", nS + nT,
+                    nS, nT, lds_main, limit,
+                    (int)(((size_t)limit - kTileBytes)/(2*64*sizeof(double))));
+    if (lds_fin > (size_t)limit)
+        return fail("%d tail entries need %zu bytes of LDS, the limit is %d "
+                    "bytes", ntail, lds_fin, limit);
+    // more than 64 KiB of dynamic LDS has to be asked for
+    if (lds_main > 65536)
+        HIP_TRY(hipFuncSetAttribute(
+            (const void *)opty_hessmv,
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
+    if (lds_fin > 65536)
+        HIP_TRY(hipFuncSetAttribute(
+            (const void *)opty_hessmv_fin,
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
+
+    auto *h = new opty_hip_hessmv;
+    h->p = p;
+    h->device = p->d.device;
+    h->d = *desc;
+    h->d.pattern = h->d.obj_pattern = nullptr;
+    h->d.inst_rows = h->d.inst_cols = h->d.tail_rows = h->d.tail_cols =
+        nullptr;
+    h->sides = sides;
+    h->nS = nS;
+    h->nT = nT;
+    h->lds_main = lds_main;
+    h->lds_fin = lds_fin;
+    auto tables = [&]() -> int {
+        if (int rc = upload(&h->d_ent, ent.data(), ent.size())) return rc;
+        if (int rc = upload(&h->d_oent, oent.data(), oent.size())) return rc;
+        if (int rc = upload(&h->d_sides, sides.data(), sides.size()))
+            return rc;
+        if (int rc = upload(&h->d_rowside, rowside.data(), rowside.size()))
+            return rc;
+        const size_t ni = (size_t)desc->nnz_inst, nt = (size_t)desc->T;
+        if (int rc = upload(&h->d_irows, (const long long *)desc->inst_rows,
+                            ni))
+            return rc;
+        if (int rc = upload(&h->d_icols, (const long long *)desc->inst_cols,
+                            ni))
+            return rc;
+        if (int rc = upload(&h->d_prows, (const long long *)desc->tail_rows,
+                            nt))
+            return rc;
+        if (int rc = upload(&h->d_pcols, (const long long *)desc->tail_cols,
+                            nt))
+            return rc;
+        // one partial per block and tail side
+        return ensure(&h->d_part, (size_t)nT*(size_t)h->blocks());
+    };
+    if (int rc = tables()) {
+        (void)opty_hip_hessmv_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int opty_hip_hessmv_destroy(opty_hip_hessmv *h) {
+    if (!h) return 0;
+    borrowed_destroy(h, {h->d_ent, h->d_oent, h->d_sides, h->d_rowside,
+                         h->d_irows, h->d_icols, h->d_prows, h->d_pcols,
+                         h->d_part, h->d_val, h->d_v, h->d_y});
+    delete h;
+    return 0;
+}
+
+int64_t opty_hip_hessmv_nnz(const opty_hip_hessmv *h) {
+    return h ? h->nnz() : -1;
+}
+
+int32_t opty_hip_hessmv_sides(const opty_hip_hessmv *h, int32_t *sides,
+                              int32_t room, int32_t *num_trajectory) {
+    if (!h) return -1;
+    const int32_t count = h->nS + h->nT;
+    if (num_trajectory) *num_trajectory = h->nS;
+    if (sides)
+        for (int32_t k = 0; k < 2*std::min(count, room); ++k)
+            sides[k] = h->sides[k];
+    return count;
+}
+
+int opty_hip_hessmv_apply(opty_hip_hessmv *h, const double *values,
+                          const double *v, double *y, int32_t mem) {
+    if (!h || !v || !y || (!values && h->nnz() > 0))
+        return fail("null argument");
+    if (int rc = borrowed_begin(h, mem, false)) return rc;
+    opty_hip_problem *p = h->p;
+    const size_t nfree = (size_t)p->num_free(), nnz = (size_t)h->nnz();
+    const long long ncn = h->ncn(), nblk = h->blocks();
+    double *out = y;
+    if (mem == OPTY_HIP_HOST) {
+        if (int rc = stage_in(h, &values, &h->d_val, nnz,
+                              std::max<size_t>(1, nnz)))
+            return rc;
+        if (int rc = stage_in(h, &v, &h->d_v, nfree, nfree)) return rc;
+        if (int rc = ensure(&h->d_y, nfree)) return rc;
+        out = h->d_y;
+    }
+    const double *ival = values + (size_t)h->d.PH*ncn;
+    const double *oval = ival + h->d.nnz_inst;
+    const double *pval = oval + (size_t)h->d.E*ncn;
+    MvArgs a{};
+    a.val = values;
+    a.oval = oval;
+    a.v = v;
+    a.y = out;
+    a.part = h->d_part;
+    a.ent = h->d_ent;
+    a.oent = h->d_oent;
+    a.sides = h->d_sides;
+    a.rowside = h->d_rowside;
+    a.N = p->d.N;
+    a.PH = h->d.PH;
+    a.E = h->d.E;
+    a.nS = h->nS;
+    a.nT = h->nT;
+    a.nrows = h->nrows();
+    hipLaunchKernelGGL(opty_hessmv, dim3((unsigned)nblk), dim3(64),
+                       h->lds_main, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (h->ntail() > 0 || h->d.nnz_inst > 0 || h->d.T > 0) {
+        FinArgs f{};
+        f.part = h->d_part;
+        f.ival = ival;
+        f.pval = pval;
+        f.v = v;
+        f.y = out;
+        f.sides = h->d_sides;
+        f.irows = h->d_irows;
+        f.icols = h->d_icols;
+        f.prows = h->d_prows;
+        f.pcols = h->d_pcols;
+        f.nblk = nblk;
+        f.tail = (long long)h->nrows()*p->d.N;
+        f.nS = h->nS;
+        f.nT = h->nT;
+        f.ntail = h->ntail();
+        f.nnz_inst = h->d.nnz_inst;
+        f.T = h->d.T;
+        hipLaunchKernelGGL(opty_hessmv_fin, dim3(1), dim3(64), h->lds_fin,
+                           h->stream, f);
+        HIP_TRY(hipGetLastError());
+    }
+    if (mem == OPTY_HIP_HOST) {
+        if (int rc = stage_out(h, y, h->d_y, nfree*sizeof(double))) return rc;
+        return host_done(h);
+    }
+    return 0;
+}
+
+}  // extern "C"

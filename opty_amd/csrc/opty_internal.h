@@ -12,6 +12,8 @@
 //   comm.cpp          RCCL communicator, broadcast of `free`, gather-v
 //   hessian.cpp       the Hessian handle (borrows a problem handle)
 //   jacprod.cpp       the Jacobian-product handle (J v, J^T w; borrows too)
+//   hessmv.cpp        the Hessian-product handle (H v from the stored
+//                     triplets; borrows too, kernels of its own)
 //   referee.cpp       (libopty_hip_referee.so) instruction-tape kernel and
 //                     register poisoner of the build verification
 #pragma once

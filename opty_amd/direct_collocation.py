@@ -1176,6 +1176,184 @@ class ConstraintCollocator(object):
             (self.num_constraints, self.num_free), dtype=np.float64,
             matvec=lambda x: apply(jvp, x), rmatvec=lambda x: apply(vjp, x))
 
+    # ------------------------------------------------------------------
+    # Hessian operator: H v from the stored triplets
+    # ------------------------------------------------------------------
+    def _hessmv_descriptor(self, objective=None):
+        """Descriptor of a :class:`hip_backend.HipHessianProduct` over the
+        constraint triplets and, with ``objective`` (a
+        :class:`hip_backend.HipObjectiveHessian`), the objective's behind
+        them."""
+        prog = self._build_hessian_program()
+        rows, cols = self.hessian_indices_closed_form()
+        N = self.num_collocation_nodes
+        at = (N - 1)*prog.PH
+        desc = dict(pattern=np.array(prog.index_pattern(), dtype=np.int32),
+                    inst_rows=rows[at:], inst_cols=cols[at:])
+        if objective is not None:
+            tail = (prog.n + prog.q)*N
+            desc.update(obj_pattern=objective.pattern,
+                        obj_base=objective.desc['base'],
+                        tail_rows=tail + objective.tail_pairs[:, 0],
+                        tail_cols=tail + objective.tail_pairs[:, 1])
+        return desc
+
+    def _ensure_hessmv(self, objective=None):
+        """The Hessian-product handle (made on first use; one for the
+        constraint triplets alone, one per objective Hessian handle)."""
+        attr = '_hessmv' if objective is None else '_hessmv_objective'
+        if objective is not None and \
+                getattr(self, '_hessmv_objective_of', None) is not objective:
+            old = getattr(self, attr, None)
+            if old is not None:
+                old.release()
+            setattr(self, attr, None)
+            self._hessmv_objective_of = objective
+
+        def create(hip):
+            return hb.HipHessianProduct(
+                hip, self._hessmv_descriptor(objective)), {}
+        # (no program of its own to hold the kernels to: the product is
+        # checked against the triplets by the test suite)
+        return self._ensure_derived(attr, create, lambda handle: None)
+
+    def _hessmv_function(self, handle):
+        """``hmv(values, v) -> y`` over ``handle``."""
+        hip = self._hip
+        nfree, nnz = self.num_free, handle.nnz
+        result = hb.pinned_empty(nfree)
+
+        def evaluate(values, v):
+            if hasattr(values, 'data_ptr'):
+                import torch
+                if tuple(values.shape) != (nnz,) or \
+                        tuple(v.shape) != (nfree,):
+                    raise ValueError('values / v have the wrong shape')
+                values = values.to(torch.float64).contiguous()
+                v = v.to(device=values.device,
+                         dtype=torch.float64).contiguous()
+                out = torch.empty(nfree, dtype=torch.float64,
+                                  device=values.device)
+                torch.cuda.current_stream(values.device).synchronize()
+                handle.apply(values, v, out, hb.DEVICE)
+                hip.synchronize()
+                return out
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            if values.shape != (nnz,):
+                raise ValueError('values must have shape ({},), got {}'
+                                 .format(nnz, values.shape))
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.shape != (nfree,):
+                raise ValueError('v must have shape ({},), got {}'.format(
+                    nfree, v.shape))
+            handle.apply(values, v, result, hb.HOST)
+            return result
+        evaluate.handle = handle
+        return evaluate
+
+    def generate_hessian_product_function(self):
+        """Returns ``hmv(values, v) -> ndarray (num_free,)``: ``H v`` on the
+        GPU, ``H`` the symmetric matrix whose lower triangle is the SUM of
+        the triplets ``values`` that the callable of
+        :meth:`generate_hessian_function` returned (order of
+        :meth:`hessian_indices`).  Every element of the result is written
+        exactly once in a fixed order of operations: the same inputs give the
+        same bits.  The result is a persistent page-locked buffer that the
+        next call overwrites.
+
+        ``values`` and ``v`` may also be torch CUDA tensors; the result is
+        then a new CUDA tensor (nothing crosses PCIe)."""
+        return self._hessmv_function(self._ensure_hessmv())
+
+    def _hessian_operator(self, handle, values):
+        """``LinearOperator`` over ``handle`` and the triplets ``values`` (a
+        CUDA tensor the operator keeps, or host values that go to a device
+        buffer of the operator's own)."""
+        from scipy.sparse.linalg import LinearOperator
+        nfree = self.num_free
+        hip = self._hip
+        if hasattr(values, 'data_ptr'):
+            import torch
+
+            def apply(x):
+                on_device = hasattr(x, 'data_ptr')
+                if on_device:
+                    x = x.to(device=values.device,
+                             dtype=torch.float64).reshape(-1).contiguous()
+                else:
+                    x = torch.from_numpy(np.ascontiguousarray(
+                        x, dtype=np.float64).reshape(-1)).to(values.device)
+                if tuple(x.shape) != (nfree,):
+                    raise ValueError('v must have shape (%d,)' % nfree)
+                out = torch.empty(nfree, dtype=torch.float64,
+                                  device=values.device)
+                torch.cuda.current_stream(values.device).synchronize()
+                handle.apply(values, x, out, hb.DEVICE)
+                hip.synchronize()
+                return out if on_device else out.cpu().numpy()
+        else:
+            values = hb.DeviceVector(values, self._device)
+            d_v = hb.DeviceVector(np.zeros(nfree), self._device)
+            d_y = hb.DeviceVector(np.zeros(nfree), self._device)
+
+            def apply(x):
+                like = x if hasattr(x, 'data_ptr') else None
+                if like is not None:
+                    x = x.detach().cpu().numpy()
+                x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+                if x.shape != (nfree,):
+                    raise ValueError('v must have shape (%d,)' % nfree)
+                d_v.assign(x)
+                handle.apply(values, d_v, d_y, hb.DEVICE)
+                hip.synchronize()
+                if like is not None:
+                    import torch
+                    return torch.from_numpy(d_y.numpy()).to(like.device)
+                return d_y.numpy()
+
+        class HessianOperator(LinearOperator):
+            """Symmetric; a torch CUDA vector is taken as it is (SciPy would
+            convert it to an array) and answered with a CUDA tensor."""
+
+            def __init__(self):
+                super().__init__(np.dtype(np.float64), (nfree, nfree))
+
+            def _matvec(self, x):
+                return apply(x)
+
+            _rmatvec = _matvec
+
+            def matvec(self, x):
+                if hasattr(x, 'data_ptr'):
+                    return apply(x)
+                return super().matvec(x)
+
+            def rmatvec(self, x):
+                if hasattr(x, 'data_ptr'):
+                    return apply(x)
+                return super().rmatvec(x)
+        op = HessianOperator()
+        op.values = values
+        op.handle = handle
+        return op
+
+    def hessian_operator(self, free, lagrange):
+        """The constraint part of the Hessian of the Lagrangian at ``(free,
+        lagrange)`` as a ``scipy.sparse.linalg.LinearOperator`` of shape
+        ``(num_free, num_free)``.  The triplets are evaluated ONCE
+        (:meth:`generate_hessian_function`) into a device buffer that the
+        operator owns -- ``.values``; a later Hessian evaluation does not
+        change its products --, and every ``matvec`` / ``rmatvec`` (the matrix
+        is symmetric) is one :meth:`generate_hessian_product_function` call on
+        them and returns a new array.  A torch CUDA ``free`` stays on the
+        device; a torch CUDA vector is answered with a CUDA tensor."""
+        if getattr(self, '_hessian_function', None) is None:
+            self._hessian_function = self.generate_hessian_function()
+        values = self._hessian_function(free, lagrange)
+        # (a CUDA result is a new tensor already; the host result is the
+        # function's persistent buffer and is copied to the device)
+        return self._hessian_operator(self._ensure_hessmv(), values)
+
     def generate_source(self):
         """HIP source of this problem's kernels and its launch metadata."""
         return self._emit(self._printer_options())
@@ -3037,6 +3215,39 @@ class Problem(object):
         self.hessianstructure = hessianstructure
         self.hessian = hessian
 
+        def hessian_operator(free, lagrange, obj_factor=1.0):
+            """The Hessian of the Lagrangian at ``(free, lagrange,
+            obj_factor)`` -- constraint triplets, then the objective's -- as
+            a ``scipy.sparse.linalg.LinearOperator`` of shape ``(num_free,
+            num_free)`` (:meth:`ConstraintCollocator.hessian_operator`): the
+            triplets are evaluated once into a device buffer that the
+            operator owns (``.values``), every product runs on the GPU.
+            Needs a device-backed ``obj_hessian``
+            (``opty_amd.create_objective_hessian_function``)."""
+            if not on_device:
+                raise TypeError(
+                    'Problem.hessian_operator needs an obj_hessian whose '
+                    'values have a device handle (values.handle: opty_amd.'
+                    'create_objective_hessian_function); a hand-written '
+                    'values callable has no index pattern to fuse.')
+            objective = values.handle
+            prog = col._build_hessian_program()
+            want = dict(N=col.num_collocation_nodes, n=prog.n, q=prog.q,
+                        r=prog.r)
+            have = {k: objective.desc[k] for k in want}
+            if have != want or prog.s:
+                raise ValueError(
+                    'the objective Hessian was built for %s, the problem '
+                    'has %s' % (have, dict(want, s=prog.s)))
+            handle = col._ensure_hessmv(objective)
+            if hasattr(free, 'data_ptr'):
+                vals = hessian(free, lagrange, obj_factor)
+            else:
+                vals = hessian(np.ascontiguousarray(free, dtype=float),
+                               lagrange, obj_factor)
+            return col._hessian_operator(handle, vals)
+        self.hessian_operator = hessian_operator
+
     bounds = property(lambda self: self._bounds)
     eom_bounds = property(lambda self: self._eom_bounds)
 
@@ -3252,6 +3463,10 @@ class ShardedProblem(Problem):
         self._group, self._root, self._torch_device = group, root, \
             torch_device
         super().__init__(*args, **kwargs)
+
+    def hessian_operator(self, free, lagrange, obj_factor=1.0):
+        raise NotImplementedError('the Hessian is not sharded: '
+                                  'ShardedProblem has no hessian_operator.')
 
     def _make_collocator(self, eom, states, num_nodes, interval, par_map,
                          traj_map, instance_constraints, time_symbol, tmp_dir,

@@ -29,7 +29,7 @@ DEFAULT_CACHE = os.path.join(_PKG, '_cache')
 ARCH = 'gfx950'
 
 #: OPTY_HIP_ABI_VERSION of include/opty_hip.h these bindings were written for
-ABI_VERSION = 10
+ABI_VERSION = 11
 HOST, DEVICE = 0, 1
 #: hipStreamLegacy: the null / legacy default stream (torch's default)
 STREAM_LEGACY = 1
@@ -75,7 +75,7 @@ def _hipcc():
 #: translation units of libopty_hip.so (csrc/opty_internal.h says what is
 #: where) and of the build referee's own library
 RUNTIME_SOURCES = ('runtime.cpp', 'programs.cpp', 'host_scatter.cpp',
-                   'comm.cpp', 'hessian.cpp', 'jacprod.cpp')
+                   'comm.cpp', 'hessian.cpp', 'jacprod.cpp', 'hessmv.cpp')
 REFEREE_SOURCES = ('referee.cpp',)
 REFEREE_PATH = os.path.join(_PKG, 'libopty_hip_referee.so')
 
@@ -396,6 +396,14 @@ class _HessDesc(ctypes.Structure):
                 ('inst_rows', ctypes.c_void_p), ('inst_cols', ctypes.c_void_p)]
 
 
+class _HessmvDesc(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'PH', 'nnz_inst', 'E', 'obj_base', 'T')] + [
+        (name, ctypes.c_void_p) for name in (
+            'pattern', 'inst_rows', 'inst_cols', 'obj_pattern', 'tail_rows',
+            'tail_cols')]
+
+
 class _JacprodDesc(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in (
         'jvp_strips', 'vjp_strips', 'num_tail', 'nnz_inst')]
@@ -532,6 +540,13 @@ _SIGNATURES = {
     'opty_hip_jacprod_destroy': (ctypes.c_int, [_P]),
     'opty_hip_jacprod_jvp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_jacprod_vjp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    'opty_hip_hessmv_create': (ctypes.c_int,
+                               [_P, ctypes.POINTER(_HessmvDesc),
+                                ctypes.POINTER(_P)]),
+    'opty_hip_hessmv_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_hessmv_nnz': (ctypes.c_int64, [_P]),
+    'opty_hip_hessmv_sides': (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P]),
+    'opty_hip_hessmv_apply': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
                                                 ctypes.c_int64]),
     'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
@@ -673,6 +688,14 @@ class DeviceVector(object):
 
     def data_ptr(self):
         return self.ptr
+
+    def assign(self, values):
+        """Overwrites the vector with ``size`` host values."""
+        host = np.ascontiguousarray(values, dtype=np.float64)
+        assert host.size == self.size
+        if host.size:
+            _check(self._lib.opty_hip_memcpy(self.ptr, host.ctypes.data,
+                                             host.nbytes, 0))
 
     def numpy(self):
         out = np.empty(self.size)
@@ -1191,6 +1214,10 @@ class HipObjectiveHessian(object):
             np.asarray(pattern, dtype=np.int32).reshape(-1),
             np.asarray(tail_pairs, dtype=np.int32).reshape(-1))))
         assert len(table) == 4*desc['E'] + 2*desc['T']
+        #: the index pattern and the parameter pairs the handle was made from
+        self.pattern = np.asarray(pattern, dtype=np.int32).reshape(-1, 4)
+        self.tail_pairs = np.asarray(tail_pairs,
+                                     dtype=np.int32).reshape(-1, 2)
         d = _ObjHessDesc(**desc)
         _check(self._lib.opty_hip_objhess_create(
             ctypes.byref(d), _ptr(table) if len(table) else None,
@@ -1247,9 +1274,10 @@ class _DerivedHandle(object):
                 raise HipBackendError('the problem handle is closed')
             d = self._descriptor()
             h = _P()
+            # (a handle without a code object of its own: ``hsaco_path`` None)
+            code = () if self._hsaco is None else (self._hsaco.encode(),)
             _check(getattr(self._lib, self._create)(
-                self._problem._h, ctypes.byref(d), self._hsaco.encode(),
-                ctypes.byref(h)))
+                self._problem._h, ctypes.byref(d), *code, ctypes.byref(h)))
             self._h = h
         return self._h
 
@@ -1317,3 +1345,58 @@ class HipJacobianProduct(_DerivedHandle):
     def vjp(self, free, w, out, mem):
         _check(self._lib.opty_hip_jacprod_vjp(self._handle(), _ptr(free),
                                               _ptr(w), _ptr(out), mem))
+
+
+class HipHessianProduct(_DerivedHandle):
+    """One ``opty_hip_hessmv`` handle: ``y = H v`` from the stored triplets of
+    the Hessian of the Lagrangian of a :class:`HipProblem`, which it borrows
+    for its sizes, device and stream (no code object: the kernels are the
+    runtime library's).  ``desc``: ``PH, pattern, inst_rows, inst_cols`` and,
+    with an objective section, ``E, obj_pattern, obj_base, tail_rows,
+    tail_cols`` (``include/opty_hip.h``).  Released and created again with
+    the problem's C handle, as the other derived handles are."""
+
+    _create, _destroy = 'opty_hip_hessmv_create', 'opty_hip_hessmv_destroy'
+
+    def __init__(self, problem, desc):
+        def table(key, dtype, width):
+            return np.ascontiguousarray(desc.get(key, ()),
+                                        dtype=dtype).reshape(-1, width)
+        self._pattern = table('pattern', np.int32, 4)
+        self._obj_pattern = table('obj_pattern', np.int32, 4)
+        self._irows, self._icols, self._trows, self._tcols = (
+            table(key, np.int64, 1) for key in
+            ('inst_rows', 'inst_cols', 'tail_rows', 'tail_cols'))
+        # (explicit counts: what the error-path tests hand over on purpose)
+        self._counts = dict(
+            PH=desc.get('PH', len(self._pattern)),
+            nnz_inst=desc.get('nnz_inst', len(self._irows)),
+            E=desc.get('E', len(self._obj_pattern)),
+            obj_base=desc.get('obj_base', 0),
+            T=desc.get('T', len(self._trows)))
+        super().__init__(problem, None)
+        self.nnz = self._lib.opty_hip_hessmv_nnz(self._h)
+
+    def _descriptor(self):
+        def ptr(a):
+            return _ptr(a) if a.size else None
+        return _HessmvDesc(
+            pattern=ptr(self._pattern), inst_rows=ptr(self._irows),
+            inst_cols=ptr(self._icols), obj_pattern=ptr(self._obj_pattern),
+            tail_rows=ptr(self._trows), tail_cols=ptr(self._tcols),
+            **{k: int(v) for k, v in self._counts.items()})
+
+    def sides(self):
+        """``(sides, number of trajectory sides)`` of the handle's side
+        table: ``(row, slot)`` pairs, ``(-1, offset)`` for a tail side."""
+        ntraj = ctypes.c_int32()
+        count = self._lib.opty_hip_hessmv_sides(self._handle(), None, 0,
+                                                ctypes.addressof(ntraj))
+        out = np.zeros((count, 2), dtype=np.int32)
+        self._lib.opty_hip_hessmv_sides(self._handle(), _ptr(out), count,
+                                        None)
+        return [tuple(int(x) for x in row) for row in out], ntraj.value
+
+    def apply(self, values, v, y, mem):
+        _check(self._lib.opty_hip_hessmv_apply(
+            self._handle(), _ptr(values), _ptr(v), _ptr(y), mem))
