@@ -173,10 +173,11 @@ typedef struct opty_hip_desc {
  * version must not call the library: the descriptor grew in 5, 6, 7 and 8
  * (8: the restricted kernels' geometry, opty_hip_output_*; 9: the
  * opty_hip_jacprod_* entry points; 10: the opty_hip_objhess_* entry points;
- * 11: the opty_hip_hessmv_* entry points), and
+ * 11: the opty_hip_hessmv_* entry points; 12: opty_hip_hessmv_apply_block
+ * and opty_hip_hessmv_block_width), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
-#define OPTY_HIP_ABI_VERSION 11
+#define OPTY_HIP_ABI_VERSION 12
 int opty_hip_abi_version(void);
 
 /* (The build verification's device side -- register poisoner, instruction
@@ -784,6 +785,15 @@ int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free,
  * 16.5 KiB tile); a pattern with more is refused at creation with a message
  * that names the count and the limit.
  *
+ * Block products Y = H V over several columns: `opty_hessmv_block<K>`, K = 2,
+ * 3, 4, keeps K values of v and K accumulators per side and lane (16 896 +
+ * 1 024*K*sides bytes of LDS), reads every value once for the K columns and
+ * applies, per column, the operations of `opty_hessmv` in its order;
+ * `opty_hessmv_block_fin` is `opty_hessmv_fin` with one block per column.  A
+ * handle's pass width is the largest of 4, 3, 2 whose LDS fits the device's
+ * limit per block, else 1; a call runs ceil(ncols / width) passes, the last one
+ * as wide as what is left (one column: the single kernels).
+ *
  * The handle BORROWS its problem handle for N, n, q, r, s, device and stream
  * (it reads none of the problem's tables) and must be destroyed before it. */
 typedef struct opty_hip_hessmv opty_hip_hessmv;
@@ -819,6 +829,19 @@ int32_t opty_hip_hessmv_sides(const opty_hip_hessmv *h, int32_t *sides,
  * for OPTY_HIP_HOST, enqueued on the problem's stream for OPTY_HIP_DEVICE. */
 int opty_hip_hessmv_apply(opty_hip_hessmv *h, const double *values,
                           const double *v, double *y, int32_t mem);
+/* Columns are contiguous vectors: column c of V at V + c*ldv, of Y at Y + c*ldy,
+ * ldv, ldy >= num_free.  Column c of Y equals, bit for bit, what
+ * opty_hip_hessmv_apply gives for column c of V; what lies between two columns
+ * of Y is not written.  Memory kinds and ordering as for opty_hip_hessmv_apply;
+ * ncols == 0 succeeds and launches nothing.  Refused before anything is
+ * enqueued: null pointers, ncols < 0, ldv or ldy below num_free, a range of Y
+ * that overlaps V or values. */
+int opty_hip_hessmv_apply_block(opty_hip_hessmv *h, const double *values,
+                                const double *V, int64_t ldv,
+                                double *Y, int64_t ldy,
+                                int32_t ncols, int32_t mem);
+/* columns one pass takes (1 .. 4), fixed at create from the LDS the side table needs */
+int32_t opty_hip_hessmv_block_width(const opty_hip_hessmv *h);
 
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);

@@ -549,6 +549,25 @@ def hessian_side_table(pattern, obj_pattern=(), obj_base=0):
             [(slot[a], slot[b]) for a, b in obj])
 
 
+#: bytes of the value tile of ``opty_hessmv`` (64 nodes, pitch 33 doubles) and
+#: of one side's ``v`` and accumulator over the 64 lanes, per column
+HESSMV_TILE_BYTES = 64*33*8
+HESSMV_SIDE_BYTES = 2*64*8
+
+
+def hessian_block_width(num_sides, lds_limit):
+    """Columns one pass of a block product ``H V`` takes: the largest ``K``
+    of 4, 3, 2 for which the LDS of ``opty_hessmv_block<K>``, ``16 896 +
+    1 024*K*num_sides`` bytes, is within ``lds_limit`` (the device's LDS per
+    block); 1 when not even two columns fit (every column then goes through
+    ``opty_hessmv``).  The rule ``opty_hip_hessmv_create`` applies."""
+    for width in (4, 3, 2):
+        if HESSMV_TILE_BYTES + HESSMV_SIDE_BYTES*width*int(num_sides) <= \
+                int(lds_limit):
+            return width
+    return 1
+
+
 def assemble_hessmv(N, num_rows, num_tail, values, v, pattern, inst_rows=(),
                     inst_cols=(), obj_pattern=(), obj_base=0, tail_rows=(),
                     tail_cols=()):

@@ -22,6 +22,12 @@
 // lane l - 1's S_R1, read from LDS; lane 0 of block 0 writes p = 0.  Lane 0 of
 // a later block repeats the previous block's last node and counts as zero in
 // the tail sums.  Every element of y is stored once; no atomics.
+//
+// Block products Y = H V (opty_hip_hessmv_apply_block): opty_hessmv_block<K>
+// keeps K columns in flight -- K values of v and K accumulators per side and
+// lane -- so that a value goes through the tile once for all K; per column the
+// operations and their order are opty_hessmv's, so column c has the bits of
+// opty_hip_hessmv_apply on column c alone.
 #include "opty_internal.h"
 
 #include <cstdint>
@@ -174,20 +180,184 @@ opty_hessmv_fin(FinArgs a) {
     for (int j = lane; j < a.ntail; j += 64) a.y[a.tail + j] = tl[j];
 }
 
+// ---- K columns per pass ------------------------------------------------------
+struct MvBlockArgs {
+    MvArgs m;               // v, y: column 0; part[(c*gridDim.x + b)*nT + t]
+    long long ldv, ldy;     // doubles between two columns of V / of Y
+};
+
+// opty_hessmv for K columns: vs and acc are [side][column][lane].  A value is
+// read from the tile (or from memory, objective section) once; both of its
+// side updates are then applied column by column.  Per column: opty_hessmv's
+// operations in opty_hessmv's order, the multiply-add pinned to the fused form
+// that opty_hessmv's `acc += x*v` is contracted to.
+template <int K>
+__global__ void __launch_bounds__(64)
+opty_hessmv_block(MvBlockArgs b) {
+    extern __shared__ double lds[];
+    const MvArgs &a = b.m;
+    const int lane = threadIdx.x;
+    const int nA = a.nS + a.nT;
+    double *tile = lds;                       // [64][kPitch]
+    double *vs = lds + 64*kPitch;             // [nA][K][64]
+    double *acc = vs + (size_t)nA*K*64;       // [nA][K][64]
+    const long long N = a.N, ncn = N - 1;
+    const long long i0 = (long long)blockIdx.x*kStride;
+    const long long i = i0 + lane;
+    const bool valid = i < ncn;
+    const long long tail = (long long)a.nrows*N;
+    const int nv = (int)(ncn - i0 < 64 ? ncn - i0 : 64);
+
+    for (int s = 0; s < nA; ++s) {
+        const int row = a.sides[2*s], off = a.sides[2*s + 1];
+        const long long at = row >= 0 ? (long long)row*N + i + off
+                                      : tail + off;
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            double x = 0.0;
+            if (valid) x = a.v[c*b.ldv + at];
+            vs[(s*K + c)*64 + lane] = x;
+            acc[(s*K + c)*64 + lane] = 0.0;
+        }
+    }
+
+    // one entry: value x on sides (sa, sb), every column
+    auto entry = [&](int sa, int sb, double x) {
+        double va[K], vb[K], t[K];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            va[c] = vs[(sa*K + c)*64 + lane];
+            vb[c] = vs[(sb*K + c)*64 + lane];
+            t[c] = acc[(sa*K + c)*64 + lane];
+        }
+#pragma unroll
+        for (int c = 0; c < K; ++c)
+            acc[(sa*K + c)*64 + lane] = fma(x, vb[c], t[c]);
+        if (sa != sb) {
+#pragma unroll
+            for (int c = 0; c < K; ++c) t[c] = acc[(sb*K + c)*64 + lane];
+#pragma unroll
+            for (int c = 0; c < K; ++c)
+                acc[(sb*K + c)*64 + lane] = fma(x, va[c], t[c]);
+        }
+    };
+
+    const double *blk = a.val + i0*a.PH;
+    const int half = lane >> 5, col = lane & 31;
+    for (int c0 = 0; c0 < a.PH; c0 += kChunk) {
+        const int w = a.PH - c0 < kChunk ? a.PH - c0 : kChunk;
+        __syncthreads();
+        if (col < w)
+            for (int nd = half; nd < nv; nd += 2)
+                tile[nd*kPitch + col] = blk[(long long)nd*a.PH + c0 + col];
+        __syncthreads();
+        for (int k = 0; k < w; ++k)
+            entry(a.ent[2*(c0 + k)], a.ent[2*(c0 + k) + 1],
+                  valid ? tile[lane*kPitch + k] : 0.0);
+    }
+
+    for (int e = 0; e < a.E; ++e)
+        entry(a.oent[2*e], a.oent[2*e + 1],
+              valid ? a.oval[(long long)e*ncn + i] : 0.0);
+    __syncthreads();
+
+    const bool writes = (lane > 0 || blockIdx.x == 0) && i <= ncn;
+    for (int R = 0; R < a.nrows; ++R) {
+        const int s0 = a.rowside[2*R], s1 = a.rowside[2*R + 1];
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            double x = 0.0;
+            if (s0 >= 0) x = acc[(s0*K + c)*64 + lane];
+            if (s1 >= 0 && lane > 0) x += acc[(s1*K + c)*64 + lane - 1];
+            if (writes) a.y[c*b.ldy + (long long)R*N + i] = x;
+        }
+    }
+
+    for (int t = 0; t < a.nT; ++t)
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            double x = acc[((a.nS + t)*K + c)*64 + lane];
+            if (lane == 0 && blockIdx.x > 0) x = 0.0;
+            for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d);
+            if (lane == 0)
+                a.part[((long long)c*gridDim.x + blockIdx.x)*a.nT + t] = x;
+        }
+}
+
+struct FinBlockArgs {
+    FinArgs f;              // part, v, y: column 0
+    long long ldv, ldy, ldpart;
+};
+
+// opty_hessmv_fin for the columns of a pass: block c is column c, with
+// opty_hessmv_fin's operations in its order.
+__global__ void __launch_bounds__(64)
+opty_hessmv_block_fin(FinBlockArgs b) {
+    extern __shared__ double tl[];          // [ntail]
+    const FinArgs &a = b.f;
+    const int lane = threadIdx.x;
+    const double *part = a.part + blockIdx.x*b.ldpart;
+    const double *v = a.v + blockIdx.x*b.ldv;
+    double *y = a.y + blockIdx.x*b.ldy;
+    for (int j = lane; j < a.ntail; j += 64) tl[j] = 0.0;
+    __syncthreads();
+    for (int t = lane; t < a.nT; t += 64) {
+        double x = 0.0;
+        for (long long k = 0; k < a.nblk; ++k) x += part[k*a.nT + t];
+        tl[a.sides[2*(a.nS + t) + 1]] = x;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        auto add = [&](long long at, double x) {
+            if (at >= a.tail) tl[at - a.tail] += x;
+            else y[at] += x;
+        };
+        auto apply = [&](long long r, long long c, double x) {
+            add(r, x*v[c]);
+            if (r != c) add(c, x*v[r]);
+        };
+        for (int k = 0; k < a.nnz_inst; ++k)
+            apply(a.irows[k], a.icols[k], a.ival[k]);
+        for (int k = 0; k < a.T; ++k)
+            apply(a.prows[k], a.pcols[k], a.pval[k]);
+    }
+    __syncthreads();
+    for (int j = lane; j < a.ntail; j += 64) y[a.tail + j] = tl[j];
+}
+
+constexpr int kMaxWidth = 4;        // widest instantiation of opty_hessmv_block
+
+// LDS of one block of a pass over `width` columns
+constexpr size_t lds_block(int sides, int width) {
+    return kTileBytes + (size_t)sides*width*2*64*sizeof(double);
+}
+
+const void *block_kernel(int width) {
+    switch (width) {
+    case 2: return (const void *)opty_hessmv_block<2>;
+    case 3: return (const void *)opty_hessmv_block<3>;
+    case 4: return (const void *)opty_hessmv_block<4>;
+    }
+    return nullptr;
+}
+
 }  // namespace
 
 struct opty_hip_hessmv : Borrowed {
     opty_hip_hessmv_desc d{};
     std::vector<int> sides;     // (row, slot) per side, trajectory sides first
     int nS = 0, nT = 0;
+    int Kb = 1;                 // columns one pass of a block product takes
     size_t lds_main = 0, lds_fin = 0;
     int *d_ent = nullptr, *d_oent = nullptr, *d_sides = nullptr,
         *d_rowside = nullptr;
     long long *d_irows = nullptr, *d_icols = nullptr, *d_prows = nullptr,
               *d_pcols = nullptr;
     double *d_part = nullptr;
-    // staging for host callers
+    // staging for host callers (v and y: cap_v / cap_y values, grown by a
+    // block product to its columns)
     double *d_val = nullptr, *d_v = nullptr, *d_y = nullptr;
+    size_t cap_v = 0, cap_y = 0;
     long long ncn() const { return p->d.N - 1; }
     long long blocks() const { return (ncn() + kStride - 1)/kStride; }
     int nrows() const { return p->d.n + p->d.q; }
@@ -238,6 +408,113 @@ int upload(T **dev, const T *host, size_t count) {
     if (!count) return 0;
     HIP_TRY(hipMalloc((void **)dev, count*sizeof(T)));
     HIP_TRY(hipMemcpy(*dev, host, count*sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// A staging vector of at least `count` values (a larger request replaces it:
+// the host calls that use it have returned, so nothing reads it any more).
+int grow(double **ptr, size_t *cap, size_t count) {
+    if (*ptr && *cap >= count) return 0;
+    if (*ptr) {
+        HIP_TRY(hipFree(*ptr));
+        *ptr = nullptr;
+        *cap = 0;
+    }
+    if (int rc = ensure(ptr, count)) return rc;
+    *cap = count;
+    return 0;
+}
+
+struct Pieces {
+    const double *ival, *oval, *pval;
+};
+
+Pieces pieces(const opty_hip_hessmv *h, const double *values) {
+    Pieces s;
+    s.ival = values + (size_t)h->d.PH*h->ncn();
+    s.oval = s.ival + h->d.nnz_inst;
+    s.pval = s.oval + (size_t)h->d.E*h->ncn();
+    return s;
+}
+
+MvArgs main_args(const opty_hip_hessmv *h, const double *values,
+                 const double *v, double *out) {
+    MvArgs a{};
+    a.val = values;
+    a.oval = pieces(h, values).oval;
+    a.v = v;
+    a.y = out;
+    a.part = h->d_part;
+    a.ent = h->d_ent;
+    a.oent = h->d_oent;
+    a.sides = h->d_sides;
+    a.rowside = h->d_rowside;
+    a.N = h->p->d.N;
+    a.PH = h->d.PH;
+    a.E = h->d.E;
+    a.nS = h->nS;
+    a.nT = h->nT;
+    a.nrows = h->nrows();
+    return a;
+}
+
+bool needs_fin(const opty_hip_hessmv *h) {
+    return h->ntail() > 0 || h->d.nnz_inst > 0 || h->d.T > 0;
+}
+
+FinArgs fin_args(const opty_hip_hessmv *h, const double *values,
+                 const double *v, double *out) {
+    const Pieces s = pieces(h, values);
+    FinArgs f{};
+    f.part = h->d_part;
+    f.ival = s.ival;
+    f.pval = s.pval;
+    f.v = v;
+    f.y = out;
+    f.sides = h->d_sides;
+    f.irows = h->d_irows;
+    f.icols = h->d_icols;
+    f.prows = h->d_prows;
+    f.pcols = h->d_pcols;
+    f.nblk = h->blocks();
+    f.tail = (long long)h->nrows()*h->p->d.N;
+    f.nS = h->nS;
+    f.nT = h->nT;
+    f.ntail = h->ntail();
+    f.nnz_inst = h->d.nnz_inst;
+    f.T = h->d.T;
+    return f;
+}
+
+// one product on the handle's stream, device pointers
+int enqueue_one(opty_hip_hessmv *h, const double *values, const double *v,
+                double *out) {
+    hipLaunchKernelGGL(opty_hessmv, dim3((unsigned)h->blocks()), dim3(64),
+                       h->lds_main, h->stream, main_args(h, values, v, out));
+    HIP_TRY(hipGetLastError());
+    if (needs_fin(h)) {
+        hipLaunchKernelGGL(opty_hessmv_fin, dim3(1), dim3(64), h->lds_fin,
+                           h->stream, fin_args(h, values, v, out));
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// `width` (2 .. Kb) columns in one pass
+int enqueue_block(opty_hip_hessmv *h, int width, const double *values,
+                  const double *V, long long ldv, double *Y, long long ldy) {
+    MvBlockArgs b{main_args(h, values, V, Y), ldv, ldy};
+    void *args[] = {&b};
+    HIP_TRY(hipLaunchKernel(block_kernel(width), dim3((unsigned)h->blocks()),
+                            dim3(64), args,
+                            lds_block(h->nS + h->nT, width), h->stream));
+    if (needs_fin(h)) {
+        FinBlockArgs f{fin_args(h, values, V, Y), ldv, ldy,
+                       (long long)h->nT*h->blocks()};
+        hipLaunchKernelGGL(opty_hessmv_block_fin, dim3((unsigned)width),
+                           dim3(64), h->lds_fin, h->stream, f);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 
@@ -339,6 +616,20 @@ int opty_hip_hessmv_create(opty_hip_problem *p,
         HIP_TRY(hipFuncSetAttribute(
             (const void *)opty_hessmv_fin,
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
+    // block products: the widest pass whose LDS fits (hessian_block_width of
+    // codegen/program.py), 1: column by column through the kernels above
+    int Kb = 1;
+    for (int w = kMaxWidth; w >= 2 && Kb == 1; --w)
+        if (lds_block(nS + nT, w) <= (size_t)limit) Kb = w;
+    for (int w = 2; w <= Kb; ++w)
+        if (lds_block(nS + nT, w) > 65536)
+            HIP_TRY(hipFuncSetAttribute(
+                block_kernel(w), hipFuncAttributeMaxDynamicSharedMemorySize,
+                (int)limit));
+    if (Kb > 1 && lds_fin > 65536)
+        HIP_TRY(hipFuncSetAttribute(
+            (const void *)opty_hessmv_block_fin,
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
 
     auto *h = new opty_hip_hessmv;
     h->p = p;
@@ -350,6 +641,7 @@ int opty_hip_hessmv_create(opty_hip_problem *p,
     h->sides = sides;
     h->nS = nS;
     h->nT = nT;
+    h->Kb = Kb;
     h->lds_main = lds_main;
     h->lds_fin = lds_fin;
     auto tables = [&]() -> int {
@@ -372,8 +664,8 @@ int opty_hip_hessmv_create(opty_hip_problem *p,
         if (int rc = upload(&h->d_pcols, (const long long *)desc->tail_cols,
                             nt))
             return rc;
-        // one partial per block and tail side
-        return ensure(&h->d_part, (size_t)nT*(size_t)h->blocks());
+        // one partial per block and tail side, and per column of a pass
+        return ensure(&h->d_part, (size_t)nT*(size_t)h->blocks()*(size_t)Kb);
     };
     if (int rc = tables()) {
         (void)opty_hip_hessmv_destroy(h);
@@ -412,65 +704,97 @@ int opty_hip_hessmv_apply(opty_hip_hessmv *h, const double *values,
     if (!h || !v || !y || (!values && h->nnz() > 0))
         return fail("null argument");
     if (int rc = borrowed_begin(h, mem, false)) return rc;
-    opty_hip_problem *p = h->p;
-    const size_t nfree = (size_t)p->num_free(), nnz = (size_t)h->nnz();
-    const long long ncn = h->ncn(), nblk = h->blocks();
+    const size_t nfree = (size_t)h->p->num_free(), nnz = (size_t)h->nnz();
     double *out = y;
     if (mem == OPTY_HIP_HOST) {
         if (int rc = stage_in(h, &values, &h->d_val, nnz,
                               std::max<size_t>(1, nnz)))
             return rc;
+        if (int rc = grow(&h->d_v, &h->cap_v, nfree)) return rc;
         if (int rc = stage_in(h, &v, &h->d_v, nfree, nfree)) return rc;
-        if (int rc = ensure(&h->d_y, nfree)) return rc;
+        if (int rc = grow(&h->d_y, &h->cap_y, nfree)) return rc;
         out = h->d_y;
     }
-    const double *ival = values + (size_t)h->d.PH*ncn;
-    const double *oval = ival + h->d.nnz_inst;
-    const double *pval = oval + (size_t)h->d.E*ncn;
-    MvArgs a{};
-    a.val = values;
-    a.oval = oval;
-    a.v = v;
-    a.y = out;
-    a.part = h->d_part;
-    a.ent = h->d_ent;
-    a.oent = h->d_oent;
-    a.sides = h->d_sides;
-    a.rowside = h->d_rowside;
-    a.N = p->d.N;
-    a.PH = h->d.PH;
-    a.E = h->d.E;
-    a.nS = h->nS;
-    a.nT = h->nT;
-    a.nrows = h->nrows();
-    hipLaunchKernelGGL(opty_hessmv, dim3((unsigned)nblk), dim3(64),
-                       h->lds_main, h->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (h->ntail() > 0 || h->d.nnz_inst > 0 || h->d.T > 0) {
-        FinArgs f{};
-        f.part = h->d_part;
-        f.ival = ival;
-        f.pval = pval;
-        f.v = v;
-        f.y = out;
-        f.sides = h->d_sides;
-        f.irows = h->d_irows;
-        f.icols = h->d_icols;
-        f.prows = h->d_prows;
-        f.pcols = h->d_pcols;
-        f.nblk = nblk;
-        f.tail = (long long)h->nrows()*p->d.N;
-        f.nS = h->nS;
-        f.nT = h->nT;
-        f.ntail = h->ntail();
-        f.nnz_inst = h->d.nnz_inst;
-        f.T = h->d.T;
-        hipLaunchKernelGGL(opty_hessmv_fin, dim3(1), dim3(64), h->lds_fin,
-                           h->stream, f);
-        HIP_TRY(hipGetLastError());
-    }
+    if (int rc = enqueue_one(h, values, v, out)) return rc;
     if (mem == OPTY_HIP_HOST) {
         if (int rc = stage_out(h, y, h->d_y, nfree*sizeof(double))) return rc;
+        return host_done(h);
+    }
+    return 0;
+}
+
+int32_t opty_hip_hessmv_block_width(const opty_hip_hessmv *h) {
+    return h ? h->Kb : -1;
+}
+
+int opty_hip_hessmv_apply_block(opty_hip_hessmv *h, const double *values,
+                                const double *V, int64_t ldv,
+                                double *Y, int64_t ldy,
+                                int32_t ncols, int32_t mem) {
+    if (!h || !V || !Y || (!values && h->nnz() > 0))
+        return fail("null argument");
+    if (ncols < 0) return fail("ncols %d < 0", ncols);
+    const int64_t num_free = h->p->num_free();
+    if (ldv < num_free)
+        return fail("ldv %lld < num_free %lld", (long long)ldv,
+                    (long long)num_free);
+    if (ldy < num_free)
+        return fail("ldy %lld < num_free %lld", (long long)ldy,
+                    (long long)num_free);
+    const size_t nfree = (size_t)num_free, nnz = (size_t)h->nnz();
+    if (ncols > 0) {
+        // [first, last) of Y against V and against values
+        auto meets = [](const double *a, size_t na, const double *b,
+                        size_t nb) {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return a0 < b0 + nb*sizeof(double) && b0 < a0 + na*sizeof(double);
+        };
+        const size_t ny = (size_t)(ncols - 1)*(size_t)ldy + nfree,
+                     nv = (size_t)(ncols - 1)*(size_t)ldv + nfree;
+        if (meets(Y, ny, V, nv))
+            return fail("Y (%d columns, ldy %lld) overlaps V (ldv %lld)",
+                        ncols, (long long)ldy, (long long)ldv);
+        if (nnz && meets(Y, ny, values, nnz))
+            return fail("Y (%d columns, ldy %lld) overlaps the %zu values",
+                        ncols, (long long)ldy, nnz);
+    }
+    if (int rc = borrowed_begin(h, mem, false)) return rc;
+    if (ncols == 0) return 0;
+    const double *dV = V;
+    double *dY = Y;
+    long long dldv = ldv, dldy = ldy;
+    if (mem == OPTY_HIP_HOST) {
+        // the columns without their padding
+        if (int rc = stage_in(h, &values, &h->d_val, nnz,
+                              std::max<size_t>(1, nnz)))
+            return rc;
+        if (int rc = grow(&h->d_v, &h->cap_v, (size_t)ncols*nfree)) return rc;
+        if (int rc = grow(&h->d_y, &h->cap_y, (size_t)ncols*nfree)) return rc;
+        for (int c = 0; c < ncols; ++c)
+            HIP_TRY(hipMemcpyAsync(h->d_v + (size_t)c*nfree,
+                                   V + (size_t)c*(size_t)ldv,
+                                   nfree*sizeof(double),
+                                   hipMemcpyHostToDevice, h->stream));
+        dV = h->d_v;
+        dY = h->d_y;
+        dldv = dldy = (long long)nfree;
+    }
+    // ceil(ncols / Kb) passes; the last one as wide as what is left
+    for (int c = 0; c < ncols; c += h->Kb) {
+        const int width = std::min(h->Kb, ncols - c);
+        const double *vc = dV + (size_t)c*(size_t)dldv;
+        double *yc = dY + (size_t)c*(size_t)dldy;
+        if (int rc = width == 1 ? enqueue_one(h, values, vc, yc)
+                                : enqueue_block(h, width, values, vc, dldv,
+                                                yc, dldy))
+            return rc;
+    }
+    if (mem == OPTY_HIP_HOST) {
+        for (int c = 0; c < ncols; ++c)
+            if (int rc = stage_out(h, Y + (size_t)c*(size_t)ldy,
+                                   h->d_y + (size_t)c*nfree,
+                                   nfree*sizeof(double)))
+                return rc;
         return host_done(h);
     }
     return 0;

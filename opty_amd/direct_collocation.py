@@ -38,6 +38,15 @@ logger = logging.getLogger(__name__)
 _METHODS = ('backward euler', 'midpoint')
 
 
+def column_major(V):
+    """``V`` (two-dimensional, either memory order, any real dtype) as a
+    column-major float64 array: column ``c`` is the ``V.shape[0]`` contiguous
+    doubles at ``c*V.shape[0]``, what ``opty_hip_hessmv_apply_block`` takes
+    with ``ldv = V.shape[0]``.  A column-major float64 ``V`` is returned as
+    it is; anything else is copied once."""
+    return np.asfortranarray(V, dtype=np.float64)
+
+
 class ConstraintCollocator(object):
     """Generates the constraint function and the sparse Jacobian of the
     constraint function of a direct-collocation transcription, evaluated on an
@@ -1251,6 +1260,62 @@ class ConstraintCollocator(object):
         evaluate.handle = handle
         return evaluate
 
+    def _hessmm_function(self, handle):
+        """``hmm(values, V) -> Y`` over ``handle``, ``V`` of shape
+        ``(num_free, k)``."""
+        hip = self._hip
+        nfree, nnz = self.num_free, handle.nnz
+
+        def evaluate(values, V):
+            if hasattr(values, 'data_ptr'):
+                import torch
+                if tuple(values.shape) != (nnz,) or V.ndim != 2 or \
+                        V.shape[0] != nfree:
+                    raise ValueError('values / V have the wrong shape')
+                values = values.to(torch.float64).contiguous()
+                # the columns of V are the rows of its transpose
+                cols = V.to(device=values.device,
+                            dtype=torch.float64).t().contiguous()
+                k = cols.shape[0]
+                out = torch.empty((k, nfree), dtype=torch.float64,
+                                  device=values.device)
+                if k:
+                    torch.cuda.current_stream(values.device).synchronize()
+                    handle.apply_block(values, cols, nfree, out, nfree, k,
+                                       hb.DEVICE)
+                    hip.synchronize()
+                return out.t()
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            if values.shape != (nnz,):
+                raise ValueError('values must have shape ({},), got {}'
+                                 .format(nnz, values.shape))
+            if np.ndim(V) != 2 or np.shape(V)[0] != nfree:
+                raise ValueError('V must have shape ({}, k), got {}'.format(
+                    nfree, np.shape(V)))
+            V = column_major(V)
+            Y = np.empty(V.shape, dtype=np.float64, order='F')
+            if V.shape[1]:
+                handle.apply_block(values, V, nfree, Y, nfree, V.shape[1],
+                                   hb.HOST)
+            return Y
+        evaluate.handle = handle
+        return evaluate
+
+    def generate_hessian_block_product_function(self):
+        """Returns ``hmm(values, V) -> ndarray (num_free, k)``: ``H V`` on
+        the GPU for the ``k`` columns of ``V`` in one call, ``H`` and
+        ``values`` as for :meth:`generate_hessian_product_function`.  The
+        handle takes ``handle.block_width`` columns per pass and reads every
+        value once per pass; column ``c`` of the result has the bits of
+        ``hmv(values, V[:, c])``.  A NumPy ``V`` in either memory order is
+        converted once to column-major; the result is a new column-major
+        float64 array.
+
+        ``values`` and ``V`` may also be torch CUDA tensors; the result is
+        then a new CUDA tensor of shape ``(num_free, k)`` (nothing crosses
+        PCIe)."""
+        return self._hessmm_function(self._ensure_hessmv())
+
     def generate_hessian_product_function(self):
         """Returns ``hmv(values, v) -> ndarray (num_free,)``: ``H v`` on the
         GPU, ``H`` the symmetric matrix whose lower triangle is the SUM of
@@ -1291,6 +1356,27 @@ class ConstraintCollocator(object):
                 handle.apply(values, x, out, hb.DEVICE)
                 hip.synchronize()
                 return out if on_device else out.cpu().numpy()
+
+            def apply_block(X):
+                on_device = hasattr(X, 'data_ptr')
+                if not on_device:
+                    X = torch.from_numpy(column_major(X).T)
+                elif X.ndim == 2:
+                    X = X.t()
+                if X.ndim != 2 or X.shape[1] != nfree:
+                    raise ValueError('X must have shape (%d, k)' % nfree)
+                # (the columns of X: the rows of its transpose)
+                X = X.to(device=values.device,
+                         dtype=torch.float64).contiguous()
+                k = X.shape[0]
+                out = torch.empty((k, nfree), dtype=torch.float64,
+                                  device=values.device)
+                if k:
+                    torch.cuda.current_stream(values.device).synchronize()
+                    handle.apply_block(values, X, nfree, out, nfree, k,
+                                       hb.DEVICE)
+                    hip.synchronize()
+                return out.t() if on_device else out.cpu().numpy().T
         else:
             values = hb.DeviceVector(values, self._device)
             d_v = hb.DeviceVector(np.zeros(nfree), self._device)
@@ -1311,9 +1397,30 @@ class ConstraintCollocator(object):
                     return torch.from_numpy(d_y.numpy()).to(like.device)
                 return d_y.numpy()
 
+            def apply_block(X):
+                like = X if hasattr(X, 'data_ptr') else None
+                if like is not None:
+                    X = X.detach().cpu().numpy()
+                if np.ndim(X) != 2 or np.shape(X)[0] != nfree:
+                    raise ValueError('X must have shape (%d, k)' % nfree)
+                X = column_major(X)
+                k = X.shape[1]
+                d_X = hb.DeviceVector(X.T, self._device)
+                d_Y = hb.DeviceVector(np.zeros(k*nfree), self._device)
+                handle.apply_block(values, d_X, nfree, d_Y, nfree, k,
+                                   hb.DEVICE)
+                hip.synchronize()
+                Y = d_Y.numpy().reshape(k, nfree).T
+                if like is not None:
+                    import torch
+                    return torch.from_numpy(Y).to(like.device)
+                return Y
+
         class HessianOperator(LinearOperator):
-            """Symmetric; a torch CUDA vector is taken as it is (SciPy would
-            convert it to an array) and answered with a CUDA tensor."""
+            """Symmetric; a torch CUDA vector, or a CUDA block of vectors of
+            shape ``(num_free, k)``, is taken as it is (SciPy would convert
+            it to an array) and answered with a CUDA tensor.  ``matmat`` is
+            one block product: bit for bit the column stack of ``matvec``."""
 
             def __init__(self):
                 super().__init__(np.dtype(np.float64), (nfree, nfree))
@@ -1322,6 +1429,16 @@ class ConstraintCollocator(object):
                 return apply(x)
 
             _rmatvec = _matvec
+
+            def _matmat(self, X):
+                return apply_block(X)
+
+            _rmatmat = _matmat
+
+            def matmat(self, X):
+                if hasattr(X, 'data_ptr'):
+                    return apply_block(X)
+                return super().matmat(X)
 
             def matvec(self, x):
                 if hasattr(x, 'data_ptr'):

@@ -29,7 +29,7 @@ DEFAULT_CACHE = os.path.join(_PKG, '_cache')
 ARCH = 'gfx950'
 
 #: OPTY_HIP_ABI_VERSION of include/opty_hip.h these bindings were written for
-ABI_VERSION = 11
+ABI_VERSION = 12
 HOST, DEVICE = 0, 1
 #: hipStreamLegacy: the null / legacy default stream (torch's default)
 STREAM_LEGACY = 1
@@ -547,6 +547,11 @@ _SIGNATURES = {
     'opty_hip_hessmv_nnz': (ctypes.c_int64, [_P]),
     'opty_hip_hessmv_sides': (ctypes.c_int32, [_P, _P, ctypes.c_int32, _P]),
     'opty_hip_hessmv_apply': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    'opty_hip_hessmv_apply_block': (ctypes.c_int,
+                                    [_P, _P, _P, ctypes.c_int64, _P,
+                                     ctypes.c_int64, ctypes.c_int32,
+                                     ctypes.c_int32]),
+    'opty_hip_hessmv_block_width': (ctypes.c_int32, [_P]),
     'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
                                                 ctypes.c_int64]),
     'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
@@ -1400,3 +1405,18 @@ class HipHessianProduct(_DerivedHandle):
     def apply(self, values, v, y, mem):
         _check(self._lib.opty_hip_hessmv_apply(
             self._handle(), _ptr(values), _ptr(v), _ptr(y), mem))
+
+    @property
+    def block_width(self):
+        """Columns one pass of :meth:`apply_block` takes (1 .. 4): the widest
+        ``opty_hessmv_block`` whose LDS fits the device's limit per block
+        (``codegen.program.hessian_block_width``)."""
+        return int(self._lib.opty_hip_hessmv_block_width(self._handle()))
+
+    def apply_block(self, values, V, ldv, Y, ldy, ncols, mem):
+        """``Y = H V`` for ``ncols`` contiguous columns, column ``c`` of
+        ``V`` at ``c*ldv`` and of ``Y`` at ``c*ldy`` doubles: bit for bit
+        what :meth:`apply` gives column by column."""
+        _check(self._lib.opty_hip_hessmv_apply_block(
+            self._handle(), _ptr(values), _ptr(V), int(ldv), _ptr(Y),
+            int(ldy), int(ncols), mem))
