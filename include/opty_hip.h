@@ -195,11 +195,41 @@ int opty_hip_list_schedule(int persist, int64_t node_blocks, int classes,
                            const float *class_cost, int32_t *table,
                            int64_t capacity, int64_t *count);
 
+/* The run schedule of a restricted kernel in run form
+ * (opty_hip_set_restricted_runs), in the same table format: per XCD the items
+ * in (block slot, class) order -- a block's classes adjacent -- cut into
+ * persist/8 CONTIGUOUS runs whose summed class costs are within one largest
+ * item of their mean.  Host arithmetic only. */
+int opty_hip_run_schedule(int persist, int64_t node_blocks, int classes,
+                          const float *class_cost, int32_t *table,
+                          int64_t capacity, int64_t *count);
+
 /* Loads the code object and allocates the device-side state (known
  * parameters, known trajectories, staging buffers). */
 int opty_hip_create(const opty_hip_desc *desc, const char *code_object_path,
                     opty_hip_problem **out);
 int opty_hip_destroy(opty_hip_problem *p);
+
+/* Replaces the handle's restricted kernels by their RUN form, which lives in
+ * a code object of its own (`code_object_path`; the handle's module keeps the
+ * dispatch form, one workgroup per block and strip, and its other kernels are
+ * what they are without this call): opty_jac_var is launched with at most
+ * `jac_persist` one-wave workgroups (a multiple of 8), each of which walks a
+ * contiguous run of (node block, strip class) items (opty_hip_run_schedule)
+ * and fills the slab / evaluates the block's sin and cos only where the block
+ * changes; `jac_class_cost[g]`, g < jac_classes, is the relative duration of
+ * strip class g (one workgroup per class and block in this form).  The same
+ * for opty_conjac_var.  The code object must carry the global `opty_run_form`
+ * and both kernels: anything else is refused, so neither form can be launched
+ * as the other.  Once per handle; a handle without the call evaluates
+ * registered outputs with the dispatch form.  (An entry point of its own:
+ * the descriptor is unchanged.) */
+int opty_hip_set_restricted_runs(opty_hip_problem *p,
+                                 const char *code_object_path,
+                                 int jac_persist, int jac_classes,
+                                 const float *jac_class_cost,
+                                 int fused_persist, int fused_classes,
+                                 const float *fused_class_cost);
 
 /* The null / legacy default stream (hipStreamLegacy) as a set_stream argument:
  * NULL itself means "the handle's own stream". */

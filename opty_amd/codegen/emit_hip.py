@@ -102,6 +102,10 @@ CON_CACHE_BYTES = 128 << 20
 #: unless asked for (EmitOptions.restricted)
 RESTRICTED_MAX_P = 2048
 
+#: global that marks a code object of the restricted kernels' run form
+#: (``opty_hip_set_restricted_runs`` refuses one without it)
+RUN_MARKER = 'opty_run_form'
+
 #: doubles between the end of a launch's Jacobian values and the wave records
 #: of ``EmitOptions.trace``
 TRACE_OFFSET = 4096
@@ -204,7 +208,23 @@ class EmitOptions(object):
                  fused_strips=None,
                  fused_order=None, deterministic=0, class_cost=None,
                  fused_class_cost=None, share_rcp=0, publish=0,
-                 var_groups=None, var_fused_groups=None, restricted=None):
+                 var_groups=None, var_fused_groups=None, restricted=None,
+                 var_order=None, var_persist=None):
+        # 'run': the restricted kernels as persistent kernels -- at most
+        # ``var_persist`` one-wave workgroups (a multiple of 8; None =
+        # RESIDENT_WAVES), each of which walks a CONTIGUOUS run of (block,
+        # strip) items, a block's strips adjacent and in entry order
+        # (csrc/runtime.cpp build_run_schedule).  Only on an item whose block
+        # differs from the one before does the wave fill the slab and
+        # evaluate the block's trig stage (every sin / cos of a slab value),
+        # whose results stay in registers for the strips that follow: a run
+        # of nine items costs two or three fills and stages instead of nine.
+        # None: one workgroup per item, dispatched by the hardware
+        assert var_order in (None, 'run')
+        self.var_order = var_order
+        self.var_persist = RESIDENT_WAVES if var_persist is None \
+            else int(var_persist)
+        assert self.var_persist >= 8 and self.var_persist % 8 == 0
         # the restricted flavour of the Jacobian kernels (emit_module): None
         # = automatic -- blocks of up to RESTRICTED_MAX_P entries: the two
         # extra kernels of a larger block (24-link systems: 5 100 entries,
@@ -480,7 +500,10 @@ class EmitOptions(object):
                 ('' if self.var_groups is None
                  else ' var_groups=%d' % self.var_groups) +
                 ('' if self.var_fused_groups is None
-                 else ' var_fused_groups=%d' % self.var_fused_groups))
+                 else ' var_fused_groups=%d' % self.var_fused_groups) +
+                ('' if self.var_order is None
+                 else ' var_order=%s var_persist=%d' % (self.var_order,
+                                                        self.var_persist)))
 
 
 def _lit(v):
@@ -1014,6 +1037,7 @@ class _ModuleWriter(object):
         self._plans = []
         self._pub = None            # publication plan (EmitOptions.publish)
         self._pub_rows = {}         # published node -> LDS row, kernel in print
+        self._staged = {}           # staged trig node -> register, run form
 
     # -- leaves -------------------------------------------------------------
     #: True while a restricted kernel is printed: its last strip may end
@@ -1418,12 +1442,12 @@ class _ModuleWriter(object):
         nothing worth skipping, a layout other than whole node-major blocks
         flushed by lines, or printer options whose machinery the restricted
         kernels do not carry (list schedules, publication, LDS parking,
-        interleaved strips, traces, the strip-dropping ablations)."""
+        interleaved strips, the strip-dropping ablations)."""
         o = self.o
         if not self.line_mode() or self.csr() or \
                 getattr(self.p, 'layout', 'coo') != 'coo' or \
                 getattr(self.p, 'pruned', False) or \
-                o.publish or o.park or o.interleave or o.trace or o.pad or \
+                o.publish or o.park or o.interleave or o.pad or \
                 'list' in (o.order, o.fused_order) or \
                 o.ablate not in (None, 'store_only', 'compute_only') or \
                 o.restricted == 0 or \
@@ -1540,6 +1564,8 @@ class _ModuleWriter(object):
         p, d = self.p, self.dag
 
         def leaf(i):
+            if i in self._staged:
+                return self._staged[i]
             if i in published:
                 return 'pub[%d + lane]' % (published[i]*TS)
             if self._is_vec_input(i):
@@ -2043,12 +2069,39 @@ class _ModuleWriter(object):
     }
 '''
 
+    def _trig_stage(self, groups, con_of_group, slab_of):
+        """Run form of the restricted kernels: ``(registers, lines)`` of the
+        block's trig stage -- every sin / cos node any wave of the kernel
+        needs whose argument is a slab value, evaluated once per block into
+        registers declared outside the item loop (``{node: name}``)."""
+        p, d = self.p, self.dag
+        roots = []
+        for grp, cons in zip(groups, con_of_group):
+            for e0, e1 in grp:
+                vend = self._virtual_end(e1) if e1 > e0 else e1
+                roots += [p.jac_out[v % p.P] for v in range(e0, vend)]
+            roots += [p.con_out[j] for j in cons]
+        needed = set(d.reachable(roots))
+        nodes = sorted(i for i in needed if d.op[i] in ('sin', 'cos') and
+                       self._is_vec_input(d.args[i][0]))
+        body = _Body(d, set(nodes), self._leaf_fn(slab_of, {}),
+                     self.o.fast_trig, self.o.deterministic)
+        body.new_scope()
+        regs = {}
+        for i in nodes:
+            regs[i] = 'tg%d' % i
+            body.lines.append('%s = %s;' % (regs[i], body.emit(i)))
+        body.end_scope()
+        return regs, body.lines
+
     def kernel(self, name, groups, con_of_group, W=1, con_nt=False,
-               inst_lines=None, first_group=0, order=None):
+               inst_lines=None, first_group=0, order=None, run=0):
         """One kernel.  ``groups`` = one list of entry strips ``(e0, e1)`` per
         wave; ``con_of_group[g]`` = constraint rows stored by wave g.  A
         workgroup is ``W`` consecutive groups of one 64-node block: they share
         one input slab (filled cooperatively) and each owns a ring tile.
+        ``run``: > 0 = the run form of a restricted kernel
+        (``EmitOptions.var_order``) with at most that many workgroups.
         ``inst_lines``: body of the instance-constraint tails, run by lane 0
         of the first workgroup AFTER the node blocks' (the runtime launches
         it only with whole-problem evaluations).  ``first_group``: the
@@ -2104,8 +2157,9 @@ class _ModuleWriter(object):
                 W = self._waves_per_workgroup(len(rows), ring_rows)
         W = max(1, min(W, G))
         order = order or self.o.order
-        listed = order == 'list' and G <= MAX_CLASSES and any(
+        listed = (order == 'list' or run) and G <= MAX_CLASSES and any(
             e1 > e0 for grp in groups for e0, e1 in grp)
+        run = run if listed else 0
         if listed:
             W = 1
         # a hand-set workgroup width that does not fit the CU's LDS (64-entry
@@ -2115,9 +2169,16 @@ class _ModuleWriter(object):
             W -= 1
         sets = (G + W - 1)//W
         self._park_rows = 0
+        stage = []
+        if run:
+            # (set while the waves' code is printed: their trig leaves)
+            self._staged, stage = self._trig_stage(
+                [g for g, k in zip(groups, keep) if k],
+                [c for c, k in zip(con_of_group, keep) if k], slab_of)
         bodies = [self._group_body(grp, con_of_group[g], slab_of)
                   if keep[g] else []
                   for g, grp in enumerate(groups)]
+        staged, self._staged = self._staged, {}
         park_rows = self._park_rows
         self.uses_park = getattr(self, 'uses_park', False) or park_rows > 0
         # Ring tiles only for the waves that stage Jacobian entries: the
@@ -2218,13 +2279,36 @@ class _ModuleWriter(object):
                '(((long long)(item & 0xffffff)*%d + grp)*8 + xcd)' % sets
                if listed else 'blockIdx.x', W),
             '        tr[0] = tr_w0; tr[1] = wall_clock64();',
-            '        tr[2] = ((long long)grp << 40) | blk;',
+            '        tr[2] = ((long long)grp << 40) | %sblk;' % (
+                # restricted kernels: wall-clock ticks (at most 65535) from
+                # the wave's / item's start to the end of its slab fill (run
+                # form: and trig stage; 0 on an item that needed neither)
+                '((tr_w1 - tr_w0 > 65535 ? 65535LL : tr_w1 - tr_w0) << 24) | '
+                if self._restricted else ''),
             '        tr[3] = ((long long)(__builtin_readcyclecounter() - '
             'tr_c0) << 24) | (long long)(__builtin_amdgcn_s_getreg('
             'GETREG_IMMED(3, 0, 20)) << 16) | (long long)'
             '__builtin_amdgcn_s_getreg(GETREG_IMMED(15, 0, 4));',
             '    }'] if self.o.trace else []
         fill = ['    ' + ln for ln in self._slab_fill(rows, slab_of, W)]
+        if self.o.trace and self._restricted:
+            # the stamp waits for the last value the fill (the stage) loaded
+            # (computed): the loads return in order
+            last = sorted(staged.values()) or (
+                ['sl%d' % rows[-1]] if W == 1 and rows else [])
+            stamp = ['    asm volatile("" :: "v"(%s));' % v for v in last]
+            stamp.append('    tr_w1 = wall_clock64();')
+        else:
+            stamp = []
+        if run:
+            # the slab and the trig stage, only when the block changes
+            fill = (['    if (blk != blk_prev) {'] + fill +
+                    ['    ' + ln for ln in stage] + stamp +
+                    ['    blk_prev = blk;', '    }'])
+        else:
+            fill += stamp
+        if stamp:
+            trace_head.append('    long long tr_w1 = tr_w0;')
         stage_weight = 0
         if pub is not None:
             assert W == G and not listed and not park_rows
@@ -2233,6 +2317,10 @@ class _ModuleWriter(object):
                 ['    ' + ln for ln in stage]
         if listed:
             # one loop around the switch: items in the order of the schedule
+            if run:
+                src += ['    long long blk_prev = -1;'] + [
+                    '    double %s = 0.0;' % r
+                    for r in sorted(staged.values())]
             src += [self._LIST_LOOP,
                     self._LIST_ITEM.format(P=self.p.P, slab=len(rows)*TS,
                                            ring=ring_rows*TS)]
@@ -2272,8 +2360,12 @@ class _ModuleWriter(object):
                           park_rows=park_rows,
                           published_rows=len(self._pub_rows),
                           publish_stage_weight=stage_weight,
-                          persist=RESIDENT_WAVES if listed else 0,
-                          class_cost=self._given_cost(name, G) or [
+                          # (``persist``: the workgroups of a LIST schedule;
+                          # a run schedule's are ``run_persist``)
+                          persist=RESIDENT_WAVES if listed and not run else 0,
+                          run_persist=run,
+                          class_cost=(None if run else
+                                      self._given_cost(name, G)) or [
                               float(sum(self._weighted_cost(e0, e1) +
                                         STORE_WEIGHT*(e1 - e0)
                                         for e0, e1 in grp if e1 > e0) +
@@ -2805,6 +2897,7 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
     # The constraint rows ride in waves of their own.
     var_ranges = w.restricted_ranges()
     var_groups = var_fused = None
+    run_parts, run_kernels = [], {}
     if var_ranges:
         # (rounded up: a restricted strip is never wider than a full one,
         # whose register budget it shares)
@@ -2825,8 +2918,23 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
                  [[] for _ in var_fused] + detached_sets, nt_fused)):
             src, meta = w.kernel(name, grp, cons, opts.waves, nt,
                                  inst_lines=folded, order='block')
+            meta['order'] = 'dispatch'
             parts += [src, '']
             kernels[key] = meta
+            if opts.var_order == 'run':
+                # the run form of the same kernel, for a code object of its
+                # own (``meta['run']``): this module, and with it the full
+                # kernels' code, stays what it is without the form.  Printed
+                # by the same writer right behind the dispatch form: the
+                # node-invariant values it reads have their table slots
+                nslots = len(w.uni_slot)
+                src, meta = w.kernel(name, grp, cons, opts.waves, nt,
+                                     inst_lines=folded, order='block',
+                                     run=opts.var_persist)
+                assert len(w.uni_slot) == nslots
+                meta['order'] = 'run' if meta['run_persist'] else 'dispatch'
+                run_parts += [src, '']
+                run_kernels[key] = meta
         w._restricted = False
     if prog.inst_con_out:
         src, meta = w.inst_kernel()
@@ -2845,6 +2953,20 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
     if opts.fast_trig == 2:
         head += [_UNIFORM_TRIG_HELPERS, '']
     source = '\n'.join(head + parts)
+    run = None
+    if run_kernels and all(k['run_persist'] for k in run_kernels.values()):
+        # (RUN_MARKER: how the library knows a code object of this form)
+        rhead = ['// generated by opty_amd.codegen.emit_hip (run form of the '
+                 'restricted kernels) -- do not edit', '// %s' % opts.key(),
+                 '#define OPTY_STORE_AUX %d' % opts.store_aux,
+                 '#include "opty_device.h"', '', _LOOP_HELPERS, '',
+                 'extern "C" __device__ __attribute__((used)) int %s = 1;'
+                 % RUN_MARKER, '']
+        if opts.fast_trig == 2:
+            rhead += [_UNIFORM_TRIG_HELPERS, '']
+        rsource = '\n'.join(rhead + run_parts)
+        run = dict(source=rsource, kernels=run_kernels,
+                   sha=hashlib.sha256(rsource.encode()).hexdigest())
     meta = dict(kernels=kernels,
                 groups=[[list(rg) for rg in grp] for grp in groups],
                 fused_groups=[[list(rg) for rg in grp] for grp in fused_jac],
@@ -2854,6 +2976,8 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
                 inst_folded=bool(folded),
                 con_attached=bool(any(attached)),
                 sha=hashlib.sha256(source.encode()).hexdigest())
+    if run:
+        meta['run'] = run
     if var_ranges:
         meta['restricted'] = dict(
             owner_ranges=[list(rg) for rg in var_ranges],

@@ -114,6 +114,13 @@ struct RegisteredOutput {
 
 struct opty_hip_problem {
     std::vector<Schedule> sched_jac, sched_fused;
+    // the restricted kernels in run form (opty_hip_set_restricted_runs): 0 =
+    // one workgroup per (block, strip), dispatched by the hardware
+    std::vector<Schedule> sched_var_jac, sched_var_fused;
+    hipModule_t run_module = nullptr;   // their code object
+    int var_jac_persist = 0, var_fused_persist = 0;
+    float var_jac_class_cost[OPTY_HIP_MAX_CLASSES] = {},
+          var_fused_class_cost[OPTY_HIP_MAX_CLASSES] = {};
     std::vector<Route> routes;
     std::vector<RegisteredOutput> outputs;
     // flavour of the last Jacobian launch per launch size (opty_hip_routing)
@@ -188,6 +195,8 @@ NodeRange whole(const opty_hip_problem *p);
 hipStream_t sync_target(hipStream_t s);
 std::vector<int> build_schedule(int persist, long long nblk, int sets,
                                 const float *cost);
+std::vector<int> build_run_schedule(int persist, long long nblk, int sets,
+                                    const float *cost);
 int launch_instance(opty_hip_problem *p, const double *free_, double *con_tail,
                     double *jac_tail);
 int eval_device(opty_hip_problem *p, int what, const double *free_,

@@ -207,14 +207,62 @@ std::vector<int> build_schedule(int persist, long long nblk, int sets,
     return table;
 }
 
+// Run schedule of a persistent restricted kernel (the printer's
+// var_order = 'run'), in the table format of build_schedule.  Per XCD the
+// items are ordered (block slot, class) -- a block's classes adjacent and in
+// class order -- and that sequence is cut into npw/8 CONTIGUOUS runs of about
+// equal summed cost (an item belongs to the run its middle falls in: every
+// run's cost is within one largest item of the mean).  Nothing is rotated
+// inside a run: a wave fills the slab and evaluates the trig stage only when
+// the block of its next item differs from the last one's, so adjacency is the
+// point.
+std::vector<int> build_run_schedule(int persist, long long nblk, int sets,
+                                    const float *cost) {
+    const long long nslot = (nblk + 7)/8;
+    const long long total = nslot*8*sets;
+    const int npw = (int)(total < persist ? total : persist);
+    const int bins = npw/8;
+    std::vector<std::vector<int>> mine((size_t)npw);
+    std::vector<double> c((size_t)sets);
+    double per_block = 0.0;
+    for (int g = 0; g < sets; ++g) {
+        c[(size_t)g] = cost[g] > 0.f ? cost[g] : 1.0;
+        per_block += c[(size_t)g];
+    }
+    for (int x = 0; x < 8 && bins > 0; ++x) {
+        const long long mine_slots = nblk > x ? (nblk - x + 7)/8 : 0;
+        const double mean = per_block*(double)mine_slots/bins;
+        double before = 0.0;
+        for (long long s = 0; s < mine_slots; ++s)
+            for (int g = 0; g < sets; ++g) {
+                long long j = (long long)((before + 0.5*c[(size_t)g])/mean);
+                if (j >= bins) j = bins - 1;
+                mine[(size_t)(j*8 + x)].push_back((g << 24) | (int)s);
+                before += c[(size_t)g];
+            }
+    }
+    std::vector<int> table;
+    table.push_back(npw);
+    int at = 0;
+    for (int w = 0; w < npw; ++w) {
+        table.push_back(at);
+        at += (int)mine[(size_t)w].size();
+    }
+    table.push_back(at);
+    for (int w = 0; w < npw; ++w)
+        table.insert(table.end(), mine[(size_t)w].begin(),
+                     mine[(size_t)w].end());
+    return table;
+}
+
 // persist > 0: a persistent kernel with a list schedule (`sched`: the
 // handle's cache of tables, one per launch size); at most `persist`
-// workgroups.
+// workgroups.  `runs`: the table is a run schedule (build_run_schedule).
 int launch(opty_hip_problem *p, hipFunction_t f, int wgs_per_block,
            int threads, const double *free_, double *con, double *jac,
            const NodeRange &rg, bool inst_block = false, int persist = 0,
            std::vector<Schedule> *sched = nullptr,
-           const float *cost = nullptr) {
+           const float *cost = nullptr, bool runs = false) {
     KernelArgs a;
     a.free_ = free_;
     a.known_traj = p->d_known;
@@ -241,8 +289,9 @@ int launch(opty_hip_problem *p, hipFunction_t f, int wgs_per_block,
             if (sc.nblk == nblk) hit = &sc;
         if (!hit) {
             // first launch of this size: build and upload (synchronous)
-            std::vector<int> table =
-                build_schedule(persist, nblk, wgs_per_block, cost);
+            std::vector<int> table = runs
+                ? build_run_schedule(persist, nblk, wgs_per_block, cost)
+                : build_schedule(persist, nblk, wgs_per_block, cost);
             Schedule sc;
             sc.nblk = nblk;
             sc.npw = table[0];
@@ -369,7 +418,9 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
     auto fused = [&] {
         if (var)
             return launch(p, p->k_conjac_var, p->d.var_fused_wgs_per_block,
-                          64*p->d.var_fused_waves_per_wg, free_, con, jac, cr);
+                          64*p->d.var_fused_waves_per_wg, free_, con, jac, cr,
+                          false, p->var_fused_persist, &p->sched_var_fused,
+                          p->var_fused_class_cost, true);
         return launch(p, p->k_conjac, p->d.fused_wgs_per_block,
                       64*p->d.fused_waves_per_wg, free_, con, jac, cr, false,
                       p->d.fused_persist, &p->sched_fused,
@@ -383,7 +434,8 @@ int calibrate_route(opty_hip_problem *p, const double *free_, double *con,
         if (var)
             return launch(p, p->k_jac_var, p->d.var_jac_wgs_per_block,
                           64*p->d.var_jac_waves_per_wg, free_, nullptr, jac,
-                          cr);
+                          cr, false, p->var_jac_persist, &p->sched_var_jac,
+                          p->var_jac_class_cost, true);
         return launch(p, p->k_jac, p->d.jac_wgs_per_block,
                       64*p->d.jac_waves_per_wg, free_, nullptr, jac, cr,
                       false, p->d.jac_persist, &p->sched_jac,
@@ -503,8 +555,18 @@ static int eval_device_impl(opty_hip_problem *p, int what,
                        : p->d.fused_wgs_per_block,
               FT = 64*(var ? p->d.var_fused_waves_per_wg
                            : p->d.fused_waves_per_wg);
-    const int jac_persist = var ? 0 : p->d.jac_persist,
-              fused_persist = var ? 0 : p->d.fused_persist;
+    // (the restricted kernels in run form: opty_hip_set_restricted_runs)
+    const int jac_persist = var ? p->var_jac_persist : p->d.jac_persist,
+              fused_persist = var ? p->var_fused_persist
+                                  : p->d.fused_persist;
+    std::vector<Schedule> *const sched_jac =
+        var ? &p->sched_var_jac : &p->sched_jac;
+    std::vector<Schedule> *const sched_fused =
+        var ? &p->sched_var_fused : &p->sched_fused;
+    const float *const jac_cost =
+        var ? p->var_jac_class_cost : p->d.jac_class_cost;
+    const float *const fused_cost =
+        var ? p->var_fused_class_cost : p->d.fused_class_cost;
     if (what != OPTY_HIP_EVAL_CON) {
         const long long nblk = (rg.end - rg.begin + 63)/64;
         bool seen = false;
@@ -575,8 +637,7 @@ static int eval_device_impl(opty_hip_problem *p, int what,
         NodeRange sr{rg.begin, rg.end, p->ncon_nodes()};
         if (int rc = launch(p, k_conjac, FS, FT, free_,
                             p->d_con_scratch + rg.begin, jac, sr, folded,
-                            fused_persist, &p->sched_fused,
-                            p->d.fused_class_cost))
+                            fused_persist, sched_fused, fused_cost, var))
             return rc;
         if (tails && !folded)
             if (int rc = launch_instance(
@@ -591,13 +652,12 @@ static int eval_device_impl(opty_hip_problem *p, int what,
             return rc;
     if (what == OPTY_HIP_EVAL_JAC || what == OPTY_HIP_EVAL_PAIR)
         if (int rc = launch(p, k_jac, S, T, free_, nullptr, jac, rg,
-                            folded, jac_persist, &p->sched_jac,
-                            p->d.jac_class_cost))
+                            folded, jac_persist, sched_jac, jac_cost, var))
             return rc;
     if (what == OPTY_HIP_EVAL_FUSED)
         if (int rc = launch(p, k_conjac, FS, FT, free_, con, jac, rg,
-                            folded, fused_persist, &p->sched_fused,
-                            p->d.fused_class_cost))
+                            folded, fused_persist, sched_fused, fused_cost,
+                            var))
             return rc;
     if (tails && !folded) {
         double *c = (what == OPTY_HIP_EVAL_JAC) ? nullptr
@@ -838,6 +898,98 @@ int opty_hip_list_schedule(int persist, int64_t node_blocks, int classes,
     return 0;
 }
 
+int opty_hip_run_schedule(int persist, int64_t node_blocks, int classes,
+                          const float *class_cost, int32_t *table,
+                          int64_t capacity, int64_t *count) {
+    if (persist < 8 || persist % 8 || node_blocks < 0 || classes < 1 ||
+        classes > OPTY_HIP_MAX_CLASSES || !class_cost || !count)
+        return fail("bad run-schedule request (%d workgroups, %lld blocks, "
+                    "%d classes)", persist, (long long)node_blocks, classes);
+    std::vector<int> t = build_run_schedule(persist, node_blocks, classes,
+                                            class_cost);
+    *count = (int64_t)t.size();
+    if (table) {
+        if (capacity < (int64_t)t.size())
+            return fail("schedule table needs %lld words",
+                        (long long)t.size());
+        memcpy(table, t.data(), t.size()*sizeof(int));
+    }
+    return 0;
+}
+
+int opty_hip_set_restricted_runs(opty_hip_problem *p,
+                                 const char *code_object_path,
+                                 int jac_persist, int jac_classes,
+                                 const float *jac_class_cost,
+                                 int fused_persist, int fused_classes,
+                                 const float *fused_class_cost) {
+    if (!p) return fail("null handle");
+    if (!code_object_path) return fail("null argument");
+    if (!p->k_jac_var || !p->k_conjac_var)
+        return fail("this module has no restricted kernels");
+    if (p->run_module)
+        return fail("the run form of this handle's restricted kernels is "
+                    "set already");
+    if (jac_persist < 8 || fused_persist < 8 || jac_persist % 8 ||
+        fused_persist % 8)
+        return fail("persistent kernels take a multiple of 8 one-wave "
+                    "workgroups (restricted: jac %d, fused %d)", jac_persist,
+                    fused_persist);
+    if (jac_classes < 1 || jac_classes > OPTY_HIP_MAX_CLASSES ||
+        !jac_class_cost || fused_classes < 1 ||
+        fused_classes > OPTY_HIP_MAX_CLASSES || !fused_class_cost)
+        return fail("a run schedule takes one cost per strip class of the "
+                    "kernel, 1 to %d (restricted: jac %d, fused %d)",
+                    OPTY_HIP_MAX_CLASSES, jac_classes, fused_classes);
+    if (int rc = use_device(p)) return rc;
+    // (tables and routes of the other form are stale)
+    HIP_TRY(hipStreamSynchronize(sync_target(p->stream)));
+    // The run form lives in a code object of its own, which says what it is:
+    // a module of the dispatch form can never be launched with a schedule,
+    // nor this one without.
+    hipModule_t mod = nullptr;
+    hipError_t e = hipModuleLoad(&mod, code_object_path);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("hipModuleLoad(%s) failed: %s", code_object_path,
+                    hipGetErrorString(e));
+    }
+    hipDeviceptr_t marker = nullptr;
+    size_t marker_bytes = 0;
+    hipFunction_t kj = nullptr, kf = nullptr;
+    if (hipModuleGetGlobal(&marker, &marker_bytes, mod, "opty_run_form") !=
+            hipSuccess ||
+        hipModuleGetFunction(&kj, mod, "opty_jac_var") != hipSuccess ||
+        hipModuleGetFunction(&kf, mod, "opty_conjac_var") != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(mod);
+        return fail("%s is not a code object of the restricted kernels' run "
+                    "form", code_object_path);
+    }
+    p->run_module = mod;
+    p->k_jac_var = kj;
+    p->k_conjac_var = kf;
+    // one one-wave workgroup per class in this form
+    p->d.var_jac_wgs_per_block = jac_classes;
+    p->d.var_fused_wgs_per_block = fused_classes;
+    p->d.var_jac_waves_per_wg = p->d.var_fused_waves_per_wg = 1;
+    for (auto *v : {&p->sched_var_jac, &p->sched_var_fused}) {
+        for (Schedule &sc : *v) (void)hipFree(sc.d_table);
+        v->clear();
+    }
+    for (size_t i = p->routes.size(); i-- > 0;)
+        if (p->routes[i].var) p->routes.erase(p->routes.begin() + (long)i);
+    p->var_jac_persist = jac_persist;
+    p->var_fused_persist = fused_persist;
+    for (int g = 0; g < OPTY_HIP_MAX_CLASSES; ++g) {
+        p->var_jac_class_cost[g] =
+            jac_persist && g < jac_classes ? jac_class_cost[g] : 0.f;
+        p->var_fused_class_cost[g] =
+            fused_persist && g < fused_classes ? fused_class_cost[g] : 0.f;
+    }
+    return 0;
+}
+
 int opty_hip_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -964,7 +1116,9 @@ int opty_hip_destroy(opty_hip_problem *p) {
                     p->d_dense, p->d_seg, p->d_con_scratch};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
-    for (auto *v : {&p->sched_jac, &p->sched_fused})
+    if (p->run_module) (void)hipModuleUnload(p->run_module);
+    for (auto *v : {&p->sched_jac, &p->sched_fused, &p->sched_var_jac,
+                    &p->sched_var_fused})
         for (Schedule &sc : *v) (void)hipFree(sc.d_table);
     // (a straggling scatter worker of the sliced mode may still read
     // h_packed: ADVICE r05)

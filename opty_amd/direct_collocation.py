@@ -196,6 +196,9 @@ class ConstraintCollocator(object):
         self._pinned = None         # (EmitOptions, hipcc switches), see
         #                             _verified_alternative
         self._built_options = None
+        # why the run form of the restricted kernels (EmitOptions.var_order)
+        # failed a build gate: the module's dispatch form then serves
+        self._run_form_refused = None
         self._tape = None           # instruction tape of the program's DAG
 
         self._sort_parameters()
@@ -1581,6 +1584,33 @@ class ConstraintCollocator(object):
                     hits = {'isa_check': str(err)}
                 if hits:
                     why = 'static ISA check: %s' % (dict(hits),)
+        run_hsaco = None
+        if why is None and meta.get('run'):
+            # the run form of the two kernels: a code object of its own
+            # (the module above is what it is without the form), held to
+            # the same static gates; one that fails them is left out and
+            # the dispatch form above serves
+            run_hsaco = self._compile(meta['run']['source'],
+                                      opt_level=opt_level)
+            spills = hb.vgpr_spills(run_hsaco, self._RESTRICTED_KERNELS)
+            refused = None
+            if spills:
+                refused = 'vector spills: %s' % (spills,)
+            else:
+                try:
+                    hits = isa_check.exec_copies(
+                        run_hsaco, list(self._RESTRICTED_KERNELS))
+                except (OSError, subprocess.SubprocessError) as err:
+                    hits = {'isa_check': str(err)}
+                if hits:
+                    refused = 'static ISA check: %s' % (dict(hits),)
+            self._run_form_refused = refused
+            if refused:
+                logger.info('the run form of the restricted kernels of %s '
+                            'is not used (%s)', os.path.basename(hsaco),
+                            refused)
+                run_hsaco = None
+        meta = dict(meta, run_hsaco=run_hsaco)
         if why:
             logger.info('the restricted kernels of %s are not used (%s)',
                         os.path.basename(hsaco), why)
@@ -2059,6 +2089,11 @@ class ConstraintCollocator(object):
         if not hot and mode == 'hot' and not force:
             return None
         side = hsaco + '.crosscheck.json'
+        if meta.get('run_hsaco'):
+            # (the verdict on a build that carries the run form of the
+            # restricted kernels is a verdict on that code object as well)
+            side = '%s.%s.crosscheck.json' % (hsaco, os.path.basename(
+                meta['run_hsaco']).replace('.hsaco', ''))
         try:
             with open(side) as f:
                 verdict = json.load(f)
@@ -2587,11 +2622,24 @@ class ConstraintCollocator(object):
             self._jacobian_layout == 'coo'
         jv, fv = (meta['kernels'][k] for k in ('jac_var', 'conjac_var')) \
             if ok else ({}, {})
-        return dict(
+        geo = dict(
             var_jac_wgs_per_block=jv.get('wgs_per_block', 0),
             var_jac_waves_per_wg=jv.get('waves_per_wg', 0),
             var_fused_wgs_per_block=fv.get('wgs_per_block', 0),
             var_fused_waves_per_wg=fv.get('waves_per_wg', 0))
+        if ok and meta.get('run_hsaco'):
+            # run form (EmitOptions.var_order): what the handle passes to
+            # opty_hip_set_restricted_runs
+            jr, fr = (meta['run']['kernels'][k]
+                      for k in ('jac_var', 'conjac_var'))
+            geo.update(
+                var_run_code_object=meta['run_hsaco'],
+                var_jac_persist=jr['run_persist'],
+                var_fused_persist=fr['run_persist'],
+                var_jac_class_cost=tuple(float(c) for c in jr['class_cost']),
+                var_fused_class_cost=tuple(
+                    float(c) for c in fr['class_cost']))
+        return geo
 
     def _routing_bits(self, meta):
         """``opty_hip_desc.routing``: the handle calibrates which kernels
@@ -2666,7 +2714,8 @@ class ConstraintCollocator(object):
         logger.info('Compiling the HIP constraint/Jacobian kernels.')
         hsaco, meta = self._build_code_object()
         try:
-            self._build_verdict = self._verify_build(hsaco, meta)
+            meta, self._build_verdict = self._verify_with_run_form(hsaco,
+                                                                   meta)
         except hb.BuildRejected as err:
             if self._emit_options is not None or self._pinned is not None:
                 raise               # the caller fixed the geometry
@@ -2680,6 +2729,24 @@ class ConstraintCollocator(object):
         for jac, a, b in getattr(self, '_owned_outputs', ()):
             hip.output_register(jac, a, b)
         return hip
+
+    def _verify_with_run_form(self, hsaco, meta):
+        """``(meta, verdict)`` of :meth:`_verify_build`.  A build that the
+        referee refuses while it carries the run form of the restricted
+        kernels is judged again without it (``meta['run_hsaco']`` None: the
+        module's dispatch form serves): the form is an extra, like the
+        restricted kernels themselves."""
+        try:
+            return meta, self._verify_build(hsaco, meta)
+        except hb.BuildRejected as err:
+            if not meta.get('run_hsaco'):
+                raise
+            logger.info('the run form of the restricted kernels of %s is '
+                        'not used (refused by the referee)',
+                        os.path.basename(hsaco))
+            self._run_form_refused = 'referee: %s' % (str(err)[:300],)
+            meta = dict(meta, run_hsaco=None)
+            return meta, self._verify_build(hsaco, meta)
 
     def _register_output(self, jac, node_begin, node_end):
         """``HipProblem.output_register`` for a device Jacobian buffer the
@@ -2703,7 +2770,8 @@ class ConstraintCollocator(object):
         self._literal_values = None
         hsaco, meta = self._build_code_object()
         try:
-            self._build_verdict = self._verify_build(hsaco, meta)
+            meta, self._build_verdict = self._verify_with_run_form(hsaco,
+                                                                   meta)
         except hb.BuildRejected as err:
             if self._emit_options is not None or self._pinned is not None:
                 raise

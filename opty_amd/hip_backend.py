@@ -346,6 +346,9 @@ class _Desc(ctypes.Structure):
             'var_fused_wgs_per_block', 'var_fused_waves_per_wg')]
 
     def __init__(self, **kw):
+        # (arguments of opty_hip_set_restricted_runs, not fields)
+        for key in HipProblem._RUN_KEYS:
+            kw.pop(key, None)
         for key in ('jac_class_cost', 'fused_class_cost'):
             cost = list(kw.pop(key, ()))
             setattr(self, key, (ctypes.c_float*32)(*cost[:32]))
@@ -364,17 +367,26 @@ def poison_registers(pattern=POISON):
     _check_referee(load_referee().opty_hip_poison_registers(pattern))
 
 
-def list_schedule(persist, node_blocks, class_cost):
+def run_schedule(persist, node_blocks, class_cost):
+    """``opty_hip_run_schedule``: the same, for a restricted kernel in run
+    form (contiguous, cost-balanced runs per XCD)."""
+    return list_schedule(persist, node_blocks, class_cost,
+                         entry='opty_hip_run_schedule')
+
+
+def list_schedule(persist, node_blocks, class_cost,
+                  entry='opty_hip_list_schedule'):
     """``opty_hip_list_schedule``: ``[[(class, block), ...] per workgroup]``
     of a persistent kernel's launch over ``node_blocks`` 64-node blocks."""
     import numpy as np
     lib = load_library()
+    build = getattr(lib, entry)
     cost = (ctypes.c_float*len(class_cost))(*class_cost)
     count = ctypes.c_int64()
-    _check(lib.opty_hip_list_schedule(persist, node_blocks, len(class_cost),
-                                      cost, None, 0, ctypes.byref(count)))
+    _check(build(persist, node_blocks, len(class_cost), cost, None, 0,
+                 ctypes.byref(count)))
     table = np.zeros(count.value, dtype=np.int32)
-    _check(lib.opty_hip_list_schedule(
+    _check(build(
         persist, node_blocks, len(class_cost), cost,
         table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(table),
         ctypes.byref(count)))
@@ -432,6 +444,14 @@ _SIGNATURES = {
         ctypes.c_int, ctypes.c_int64, ctypes.c_int,
         ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
         ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    'opty_hip_run_schedule': (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
+        ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    'opty_hip_set_restricted_runs': (ctypes.c_int, [
+        _P, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+        ctypes.POINTER(ctypes.c_float),
+        ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     'opty_hip_create': (ctypes.c_int, [ctypes.POINTER(_Desc),
                                        ctypes.c_char_p,
                                        ctypes.POINTER(_P)]),
@@ -799,15 +819,40 @@ class HipProblem(object):
         if self._lib.opty_hip_device_count() == 0:
             raise HipBackendError('no HIP device is visible: the HIP '
                                   'backend has no CPU fallback')
-        self._h = _P()
-        d = _Desc(**desc)
-        _check(self._lib.opty_hip_create(ctypes.byref(d),
-                                         hsaco_path.encode(),
-                                         ctypes.byref(self._h)))
+        self._h = self._create(desc, hsaco_path)
         self.desc = dict(desc)
         self.num_free = self._lib.opty_hip_num_free(self._h)
         self.num_constraints = self._lib.opty_hip_num_constraints(self._h)
         self.nnz = self._lib.opty_hip_nnz(self._h)
+
+    #: descriptor keys of the restricted kernels' run form: not fields of
+    #: ``opty_hip_desc`` but arguments of ``opty_hip_set_restricted_runs``
+    _RUN_KEYS = ('var_jac_persist', 'var_fused_persist',
+                 'var_jac_class_cost', 'var_fused_class_cost',
+                 'var_run_code_object')
+
+    def _create(self, desc, hsaco_path):
+        """A new C handle for ``desc``; where the build carries the run form
+        of the restricted kernels (``var_run_code_object``: a code object of
+        its own) the handle takes it before anything can launch them."""
+        desc = dict(desc)
+        run = {k: desc.pop(k, None) for k in self._RUN_KEYS}
+        h = _P()
+        d = _Desc(**desc)
+        _check(self._lib.opty_hip_create(ctypes.byref(d),
+                                         hsaco_path.encode(),
+                                         ctypes.byref(h)))
+        if run['var_run_code_object']:
+            jp, fp = (int(run[k] or 0) for k in self._RUN_KEYS[:2])
+            jc, fc = (list(run[k] or ()) for k in self._RUN_KEYS[2:4])
+            rc = self._lib.opty_hip_set_restricted_runs(
+                h, run['var_run_code_object'].encode(),
+                jp, len(jc), (ctypes.c_float*max(1, len(jc)))(*jc),
+                fp, len(fc), (ctypes.c_float*max(1, len(fc)))(*fc))
+            if rc:
+                self._lib.opty_hip_destroy(h)
+                _check(rc)
+        return h
 
     def close(self):
         # Hessian handles borrow this one: they go first
@@ -823,10 +868,7 @@ class HipProblem(object):
         """Replaces the C handle behind this object by one for another code
         object of the same problem (kernels specialised for new parameter
         values); tables and stream have to be installed again."""
-        new = _P()
-        d = _Desc(**desc)
-        _check(self._lib.opty_hip_create(ctypes.byref(d), hsaco_path.encode(),
-                                         ctypes.byref(new)))
+        new = self._create(desc, hsaco_path)
         self.close()
         self._h = new
         self.desc = dict(desc)

@@ -486,6 +486,12 @@ def tune(collocator, iters=60, rounds=5, save=True, path=None, log=None,
     # (opty_hip_desc.jac_via_fused), by more than run-to-run noise
     jac_via_fused = fused_pays and \
         best['fused'][0] < best['jac'][0]*0.99 - 3e-4
+    # what this tuner does not measure stays as the plan had it: the form of
+    # the restricted kernels (tools/restricted_runs.py measures it)
+    kept = (lookup_entry(prog, blocks) or {}).get('options', {})
+    for tag in ('var_order', 'var_persist', 'var_groups', 'var_fused_groups'):
+        if tag in kept and tag not in options:
+            options[tag] = kept[tag]
     entry = dict(options=options, fused_pays=bool(fused_pays),
                  jac_via_fused=bool(jac_via_fused),
                  seed=dict(jac=geo['jac'], fused=geo['fused']),
