@@ -18,8 +18,6 @@ follows the reference's rules so that ``constraints(free)``,
 import logging
 import os
 
-import subprocess
-
 import numpy as np
 import sympy as sm
 import sympy.physics.mechanics as me
@@ -29,7 +27,9 @@ from .codegen.program import build_program, build_hessian_program, \
     build_jacobian_product_program, \
     varying_copies
 from .codegen.emit_hip import emit_module, EmitOptions
+from . import build_ladder as bl
 from . import hip_backend as hb
+from . import isa_check
 
 __all__ = ['Problem', 'ConstraintCollocator', 'ShardedProblem']
 
@@ -651,48 +651,14 @@ class ConstraintCollocator(object):
         (a hit: the uniform-sincos sibling is built in its place when it is
         clean).  A module that spills whatever the cut is refused."""
         from .codegen.emit_hessian import emit_hessian_module
-        hsaco, cut, meta = self._build_spill_free_module(
-            emit_hessian_module, self._build_hessian_program(),
+        hsaco, cut, meta = bl.spill_free_module(
+            emit_hessian_module, self._build_hessian_program(), self._compile,
             ('opty_hess', 'opty_hess_inst'), self._HESS_STRIP_OPS)
         if hsaco is None:
             raise hb.HipBackendError(
                 'every build of the Hessian kernels spills vector registers: '
                 '%s' % meta['tried'])
         return hsaco, cut, dict(meta, strips=len(cut))
-
-    def _build_spill_free_module(self, emit, prog, names, budget):
-        """``(hsaco, cut(s), meta)`` of a derived program's module, from
-        ``emit(prog, budget, forget, fast_trig=1) -> (source, cut(s))``: the
-        first build whose kernels ``names`` spill no vector register (the
-        strip budget halved down to 200, then ``forget``; six tries), through
-        the static ISA check (a hit: the uniform-sincos sibling is built in
-        its place when it is clean).  ``hsaco`` is None and ``meta['tried']``
-        lists the builds when every one of them spills."""
-        from . import isa_check
-        forget = False
-        tried = []
-        for _ in range(6):
-            source, cut = emit(prog, budget, forget)
-            hsaco = self._compile(source)
-            spills = hb.vgpr_spills(hsaco, names)
-            tried.append((budget, forget, spills))
-            if not spills:
-                break
-            if budget > 200:
-                budget //= 2
-            else:
-                forget = True
-        else:
-            return None, None, dict(tried=tried)
-        hits = isa_check.exec_copies(hsaco, names)
-        if hits:
-            src2, cut2 = emit(prog, budget, forget, fast_trig=2)
-            twin = self._compile(src2)
-            if not hb.vgpr_spills(twin, names) and \
-                    not isa_check.exec_copies(twin, names):
-                hsaco, cut, hits = twin, cut2, {}
-        return hsaco, cut, dict(strip_ops=budget, forget=forget,
-                                isa_exec_copies=hits)
 
     #: constraint nodes the referee compares: the first wave and the last node
     _HESS_VERIFY_NODES = 64
@@ -947,8 +913,8 @@ class ConstraintCollocator(object):
         uniform-sincos sibling is built in its place when it is clean).  A
         module that spills whatever the cut is refused."""
         from .codegen.emit_jacprod import emit_jacprod_module
-        hsaco, cuts, meta = self._build_spill_free_module(
-            emit_jacprod_module, self._build_jacprod_program(),
+        hsaco, cuts, meta = bl.spill_free_module(
+            emit_jacprod_module, self._build_jacprod_program(), self._compile,
             self._JACPROD_KERNELS, self._JACPROD_STRIP_OPS)
         if hsaco is None:
             raise hb.BuildRejected(
@@ -1565,45 +1531,23 @@ class ConstraintCollocator(object):
         the static ISA check, or sits next to a banned full kernel is used
         WITHOUT them (the descriptor says the module has none, registered
         outputs are written whole) -- never rebuilt for their sake."""
-        from . import isa_check
         hsaco, meta = self._build_checked(opt_level)
         if 'jac_var' not in meta['kernels']:
             return hsaco, meta
-        why = None
         if meta.get('banned_kernels'):
             why = 'full kernels banned: %s' % (meta['banned_kernels'],)
         else:
-            spills = hb.vgpr_spills(hsaco, self._RESTRICTED_KERNELS)
-            if spills:
-                why = 'vector spills: %s' % (spills,)
-            else:
-                try:
-                    hits = isa_check.exec_copies(
-                        hsaco, list(self._RESTRICTED_KERNELS))
-                except (OSError, subprocess.SubprocessError) as err:
-                    hits = {'isa_check': str(err)}
-                if hits:
-                    why = 'static ISA check: %s' % (dict(hits),)
+            why = bl.static_gate(hsaco, self._RESTRICTED_KERNELS).refusal()
         run_hsaco = None
         if why is None and meta.get('run'):
             # the run form of the two kernels: a code object of its own
             # (the module above is what it is without the form), held to
-            # the same static gates; one that fails them is left out and
-            # the dispatch form above serves
+            # the same static gate; one that fails it is left out and the
+            # dispatch form above serves
             run_hsaco = self._compile(meta['run']['source'],
                                       opt_level=opt_level)
-            spills = hb.vgpr_spills(run_hsaco, self._RESTRICTED_KERNELS)
-            refused = None
-            if spills:
-                refused = 'vector spills: %s' % (spills,)
-            else:
-                try:
-                    hits = isa_check.exec_copies(
-                        run_hsaco, list(self._RESTRICTED_KERNELS))
-                except (OSError, subprocess.SubprocessError) as err:
-                    hits = {'isa_check': str(err)}
-                if hits:
-                    refused = 'static ISA check: %s' % (dict(hits),)
+            refused = bl.static_gate(
+                run_hsaco, self._RESTRICTED_KERNELS).refusal()
             self._run_form_refused = refused
             if refused:
                 logger.info('the run form of the restricted kernels of %s '
@@ -1617,80 +1561,91 @@ class ConstraintCollocator(object):
         return hsaco, dict(meta, restricted_ok=why is None,
                            restricted_refused=why)
 
+    _FULL_KERNELS = ('opty_con', 'opty_jac', 'opty_conjac')
+
     def _build_checked(self, opt_level=None):
-        """The code object this collocator uses: :meth:`_build_spill_free`'s,
-        unless the static ISA check (``opty_amd.isa_check``: a vector
-        register copied into an accumulation register under a narrowed EXEC
-        and read back under a wider one -- the hipcc 7.2 fault of DESIGN.md
-        4.1 that is understood at the instruction) finds such a copy in one
-        of its kernels.  Then the same geometry printed with ``fast_trig=2``
-        (sincos behind a wave-uniform test: no EXEC-narrowing if / else on
-        the hot path, which is where the copies sit) is built, and used when
-        it is clean -- no such copy, no vector spills --, BEFORE any GPU time
-        is spent on either.  ``meta['isa_exec_copies']``
-        carries the count of the build in use; the referee judges it like
-        any other build.
+        """The code object this collocator uses, ``(hsaco, meta)``:
+        :meth:`_build_spill_free`'s, unless the static ISA check
+        (``opty_amd.isa_check``: a vector register copied into an
+        accumulation register under a narrowed EXEC and read back under a
+        wider one -- the hipcc 7.2 fault of DESIGN.md 4.1 that is understood
+        at the instruction) finds such a copy in one of its kernels.  Then
+        the same geometry printed with ``fast_trig=2`` (sincos behind a
+        wave-uniform test: no EXEC-narrowing if / else on the hot path, which
+        is where the copies sit) is built, and used when it is clean -- no
+        such copy, no vector spills --, BEFORE any GPU time is spent on
+        either.  ``meta['isa_exec_copies']`` carries
+        the count of the build in use (None: the LLVM tools failed); the
+        referee judges it like any other build.
 
         Before that: automatic parameter specialisation
         (``specialize_parameters=None``) -- when the generic module's fused
         kernel spills ``_AUTO_SPECIALIZE_SGPR_SPILLS`` scalar registers or
         more, the module with the known parameters printed as literals is
         built in its place (:meth:`_wants_auto_specialization`)."""
-        import copy
-        from . import isa_check
-        hsaco, meta = self._build_spill_free(opt_level)
-        if self._wants_auto_specialization(hsaco, opt_level):
+        build = self._build_spill_free(opt_level)
+        if self._wants_auto_specialization(build.hsaco, opt_level):
             # the generic module of this problem is of the class that gains
             # from literals: build (and from here on use) the specialised one
             logger.info('the generic kernels spill %d scalar registers: '
                         'using parameter-specialised kernels '
                         '(specialize_parameters=None: automatic)',
-                        hb.cached_kernel_resources(hsaco)['opty_conjac'][
-                            '.sgpr_spill_count'])
+                        hb.cached_kernel_resources(build.hsaco)[
+                            'opty_conjac']['.sgpr_spill_count'])
             self._specialize = self._auto_specialized = True
             self._specialized_for = self._literal_values = None
-            hsaco, meta = self._build_spill_free(opt_level)
+            build = self._build_spill_free(opt_level)
         if self._auto_specialized:
-            meta = dict(meta, auto_specialized=True)
+            build = build._replace(
+                meta=dict(build.meta, auto_specialized=True))
+        build = self._uniform_sibling_if_better(build, opt_level)
+        self._built_source, self._built_options = build.source, build.options
+        return build.hsaco, build.meta
+
+    def _uniform_sibling_if_better(self, build, opt_level):
+        """``build`` through the static ISA check of its full kernels, or
+        its clean ``fast_trig=2`` sibling (:meth:`_build_checked`)."""
+        hsaco, meta = build.hsaco, build.meta
         banned = set(meta.get('banned_kernels', ()))
-        names = [k for k in ('opty_con', 'opty_jac', 'opty_conjac')
-                 if k not in banned]
-        try:
-            hits = isa_check.exec_copies(hsaco, names)
-        except (OSError, subprocess.SubprocessError) as err:
-            logger.warning('static ISA check of %s failed: %s', hsaco, err)
-            return hsaco, dict(meta, isa_exec_copies=None)
-        meta = dict(meta, isa_exec_copies=dict(hits))
-        base = self._built_options
+        gate = bl.static_gate(hsaco, self._FULL_KERNELS, ignore=banned,
+                              spills=build.spills)
+        if gate.error is not None:
+            logger.warning('static ISA check of %s failed: %s', hsaco,
+                           gate.error)
+            return build._replace(meta=dict(meta, isa_exec_copies=None))
+        hits = gate.copies
+        build = build._replace(meta=dict(meta, isa_exec_copies=dict(hits)))
         if not hits or self._emit_options is not None or \
-                self._pinned_build() is not None or base is None or \
-                base.fast_trig == 2 or opt_level is not None:
-            return hsaco, meta
+                self._pinned_build() is not None or \
+                build.options.fast_trig == 2 or opt_level is not None:
+            return build
         if isa_check.noted(hsaco, 'sibling_no_better'):
             # (found out by an earlier build of the same module)
-            return hsaco, meta
-        trial = copy.copy(base)
-        trial.fast_trig = 2
-        source, tmeta = self._emit(trial)
-        twin = self._compile(source)
-        spills = {k: v for k, v in hb.vgpr_spills(twin).items()
-                  if k not in banned}
-        thits = isa_check.exec_copies(twin, names)
-        if spills or thits:
+            return build
+        twin = self._trials().build(build.options, dict(fast_trig=2))
+        spills = {k: v for k, v in twin.spills.items() if k not in banned}
+        gate = bl.static_gate(twin.hsaco, self._FULL_KERNELS, ignore=banned,
+                              spills=spills)
+        if gate.error is not None:
+            # (no note: a later build tries again)
+            logger.info('static ISA check: %s in %s; its uniform-sincos '
+                        'sibling could not be checked (%s): kept', hits,
+                        os.path.basename(hsaco), gate.error)
+            return build
+        if not gate.clean:
             logger.info('static ISA check: %s in %s; the uniform-sincos '
                         'sibling is no better (copies %s, spills %s): kept',
-                        hits, os.path.basename(hsaco), thits, spills)
+                        hits, os.path.basename(hsaco), gate.copies, spills)
             isa_check.note(hsaco, 'sibling_no_better',
-                           dict(copies=thits, spills=spills))
-            return hsaco, meta
+                           dict(copies=gate.copies, spills=spills))
+            return build
         logger.info('static ISA check: %s in %s: replaced by the uniform-'
                     'sincos sibling %s (clean)', hits,
-                    os.path.basename(hsaco), os.path.basename(twin))
-        self._built_source, self._built_options = source, trial
+                    os.path.basename(hsaco), os.path.basename(twin.hsaco))
         keep = {k: meta[k] for k in ('banned_kernels', 'vector_spills',
                                      'auto_specialized') if k in meta}
-        return twin, dict(tmeta, isa_exec_copies={}, isa_replaced=dict(hits),
-                          **keep)
+        return twin._replace(meta=dict(
+            twin.meta, isa_exec_copies={}, isa_replaced=dict(hits), **keep))
 
     #: spilled scalar registers of the generic fused kernel from which the
     #: parameter-specialised module is used automatically
@@ -1719,146 +1674,38 @@ class ConstraintCollocator(object):
             return False
         return spilled >= self._AUTO_SPECIALIZE_SGPR_SPILLS
 
+    def _trials(self):
+        return bl.TrialBuilder(self._emit, self._compile)
+
     def _build_spill_free(self, opt_level=None):
-        """Emits and compiles this problem's module; returns ``(hsaco path,
-        meta)``.  Unless the caller fixed the printer options, a build whose
-        kernels spill VECTOR registers to scratch memory is not used (see
-        ``hip_backend.vgpr_spills``): the constraint rows are re-cut by
-        count, then the strips of the spilling kernels are made narrower,
-        until a build is spill-free."""
-        import copy
+        """Emits and compiles this problem's module; returns the
+        ``build_ladder.Build``.  Unless the caller fixed the printer options,
+        a build whose kernels spill VECTOR registers to scratch memory is not
+        used (see ``hip_backend.vgpr_spills``): the constraint rows are
+        re-cut by count, then the strips of the spilling kernels are made
+        narrower, until a build is spill-free
+        (``build_ladder.spill_free``)."""
+        trials = self._trials()
         pinned = self._pinned_build()
         if pinned is not None and opt_level is None:
             # a build that replaced one the verification refused
             # (_verified_alternative): reproduced exactly as recorded
-            opts, how = pinned
-            source, meta = self._emit(opts)
-            hsaco = self._compile(
-                source, opt_level=how.get('opt_level'),
-                extra_flags=tuple(how.get('extra_flags', ())))
-            self._built_source, self._built_options = source, opts
-            return hsaco, meta
-        opts = self._printer_options()
-        source, meta = self._emit(opts)
-        hsaco = self._compile(source, opt_level=opt_level)
-        self._built_source, self._built_options = source, opts
+            return trials.build(pinned[0], how=pinned[1])
+        best = trials.build(self._printer_options(),
+                            how=dict(opt_level=opt_level))
         if self._emit_options is not None:
             # the caller fixed the geometry: it is built as asked, but never
             # silently -- this is the build class that returned wrong values
-            spills = hb.vgpr_spills(hsaco)
-            if spills:
+            if best.spills:
                 logger.warning(
                     'emit_options give kernels that spill vector registers '
                     'to scratch memory (%s); such builds have returned wrong '
                     'values (DESIGN.md 4.1): drop emit_options, or verify '
-                    'with ConstraintCollocator.cross_check()', spills)
-            return hsaco, meta
-        best = (hsaco, meta, hb.vgpr_spills(hsaco), (source, meta), opts)
-        geo = meta['geometry']
-        # where spills appear is erratic in the cut (24-link stand-in, fused
-        # strips 18 ... 28: only 20, 25 and 28 are spill-free), so the
-        # narrower cuts are tried a few at a time, in parallel (hipcc is a
-        # subprocess), and the first spill-free one in this order wins
-        steps = []
-        if geo['con_waves'] > 1 and opts.con_split == 'work':
-            steps.append(0)
-        if geo['line_mode'] or self._jacobian_layout == 'csr':
-            # (row-sorted blocks are cut at row starts: any count up to M)
-            steps += [1, 2, 3, 4, 5, 6, 8, 10, 12]
-
-        def attempt(d, detach=False, forget=False):
-            trial = copy.copy(opts)
-            if geo['con_waves'] > 1:
-                trial.con_split = 'count'
-            if forget:
-                # 16-entry chunks whose temporaries are dropped at every
-                # chunk boundary: what the chunks share is evaluated again,
-                # the live values of a wave are those of 16 entries (the
-                # midpoint rule of the muscle-driven leg: 24 spilled registers
-                # at every cut otherwise, none this way)
-                trial.forget, trial.chunk = 1, 16
-            if detach:
-                # constraint rows back in waves of their own: the Jacobian
-                # waves they rode in (arithmetic-bound blocks, emit_hip.
-                # _attach_constraint_rows) get their registers back
-                trial.con_attach = 0
-            if d and geo.get('cut') == 'work':
-                # more strips would only split the store-only part of a
-                # work-aware cut: its arithmetic strips get a smaller
-                # register budget instead (the strip count follows)
-                from .codegen.emit_hip import WORK_CUT_MAX_LIVE
-                trial.work_live = max(40, WORK_CUT_MAX_LIVE - 12*d)
-            elif d:
-                trial.groups = geo['jac'] + (d if 'opty_jac' in best[2]
-                                             else 0)
-                trial.fused_groups = geo['fused'] + (
-                    d if 'opty_conjac' in best[2] else 0)
-            if self._deterministic:
-                trial.deterministic = 1
-            source, meta = self._emit(trial)
-            hsaco = self._compile(source, opt_level=opt_level)
-            return hsaco, meta, hb.vgpr_spills(hsaco), (source, meta), trial
-
-        from concurrent.futures import ThreadPoolExecutor
-        if opts.park and best[2]:
-            # a planned wave (LDS parking) that spills: other register
-            # budgets of the plan first -- where spills appear is erratic --,
-            # then the same options without the merged strips / parking
-            def replanned(live):
-                trial = copy.copy(opts)
-                if live is None:
-                    trial.park, trial.fused_strips = 0, None
-                else:
-                    trial.park_live = live
-                if self._deterministic:
-                    trial.deterministic = 1
-                source, meta = self._emit(trial)
-                hsaco = self._compile(source, opt_level=opt_level)
-                return (hsaco, meta, hb.vgpr_spills(hsaco), (source, meta),
-                        trial)
-            lives = [opts.park_live + d for d in (10, -10, -20, -30)
-                     if opts.park_live + d > 100] + [None]
-            logger.info('kernels %s of a plan with LDS parking spill vector '
-                        'registers: other register budgets %s', sorted(
-                            best[2]), lives)
-            with ThreadPoolExecutor(len(lives)) as pool:
-                results = list(pool.map(replanned, lives))
-            clean = [r for r in results if not r[2]]
-            # (a plan that needs more than a quarter of a CU's LDS per wave
-            # costs resident waves: the unmerged fallback comes before it)
-            clean.sort(key=lambda r: max(
-                k['lds_bytes'] for k in r[1]['kernels'].values()) > 40*1024)
-            if clean:
-                best = clean[0]
-                opts, meta = best[4], best[1]
-                geo = meta['geometry']
-        phases = [(False, False, list(steps))]
-        detachable = bool(meta.get('con_attached')) and \
-            opts.con_attach is None
-        if detachable:
-            phases.append((True, False, [0] + [d for d in steps if d]))
-        if geo['line_mode'] and opts.chunk == 32 and not opts.forget:
-            phases.append((detachable, True, [0, 2, 4, 8]))
-        for detach, forget, todo in phases:
-            while best[2] and todo:
-                batch, todo = todo[:4], todo[4:]
-                logger.info('kernels %s spill vector registers: rebuilding '
-                            'with narrower cuts %s%s%s', sorted(best[2]),
-                            batch,
-                            ', constraint rows detached' if detach else '',
-                            ', temporaries dropped per chunk' if forget
-                            else '')
-                with ThreadPoolExecutor(len(batch)) as pool:
-                    results = list(pool.map(
-                        lambda d: attempt(d, detach, forget), batch))
-                clean = [r for r in results if not r[2]]
-                if clean:
-                    best = clean[0]
-                else:
-                    least = min(results, key=lambda r: sum(r[2].values()))
-                    if sum(least[2].values()) < sum(best[2].values()):
-                        best = least
-        if best[2] and set(best[2]) in ({'opty_jac'}, {'opty_conjac'}) and \
+                    'with ConstraintCollocator.cross_check()', best.spills)
+            return best
+        best = bl.spill_free(trials, best, self._jacobian_layout)
+        if best.spills and \
+                set(best.spills) in ({'opty_jac'}, {'opty_conjac'}) and \
                 self._jacobian_layout in ('coo', 'csr'):
             # ONE of the two Jacobian kernels spills whatever the cut, the
             # other is clean (the biped's 6 250-node shard: opty_jac, 2
@@ -1866,16 +1713,16 @@ class ConstraintCollocator(object):
             # handle routes its entry point through the clean one
             # (opty_hip_desc.routing: OPTY_HIP_ROUTE_NO_*), every wrong
             # build of r03 was of this class.
-            banned = sorted(best[2])
+            banned = sorted(best.spills)
             logger.info('kernel %s spills vector registers whatever the cut '
                         '(%s): it will not be launched, %s serves its entry '
-                        'point', banned[0], best[2],
+                        'point', banned[0], best.spills,
                         'opty_conjac' if banned == ['opty_jac']
                         else 'opty_con + opty_jac')
-            self._built_source, self._built_options = best[3][0], best[4]
-            return best[0], dict(best[1], banned_kernels=banned,
-                                 vector_spills=dict(best[2]))
-        if best[2]:
+            return best._replace(meta=dict(
+                best.meta, banned_kernels=banned,
+                vector_spills=dict(best.spills)))
+        if best.spills:
             # No cut is spill-free (a system larger than anything in the
             # zoo).  The wrong values of round 3 followed one stage of the
             # pre-RA scheduler, which only runs for such kernels; every build
@@ -1883,21 +1730,18 @@ class ConstraintCollocator(object):
             # not (profiles/r03_spill_incident.txt).  So the last resort is
             # the least-spilling cut built WITHOUT that stage -- and a loud
             # warning: run ``cross_check()`` on such a problem.
-            source, meta = best[3]
             hsaco = self._compile(
-                source, extra_flags=hb.SAFE_SCHEDULER_FLAGS,
+                best.source, extra_flags=hb.SAFE_SCHEDULER_FLAGS,
                 opt_level=opt_level)
             logger.warning('kernels %s spill vector registers to scratch '
                            'memory whatever the cut (%d states, %d entries '
                            'per block, launches of %d blocks): built with %s; '
                            'verify with ConstraintCollocator.cross_check()',
-                           best[2], self.num_states, self._program.P,
+                           best.spills, self.num_states, self._program.P,
                            self._launch_blocks(),
                            ' '.join(hb.SAFE_SCHEDULER_FLAGS))
-            self._built_source, self._built_options = source, best[4]
-            return hsaco, meta
-        self._built_source, self._built_options = best[3][0], best[4]
-        return best[0], best[1]
+            return best._replace(hsaco=hsaco)
+        return best
 
     def _pinned_build(self):
         """``(EmitOptions, {'opt_level': .., 'extra_flags': ..})`` of the
@@ -1925,8 +1769,9 @@ class ConstraintCollocator(object):
         hipcc's faults at the register limit are erratic in the cut -- the
         biped's default 20 strips are wrong in strip 17, identically in both
         Jacobian kernels, while 12, 24 and 32 strips, 16-entry chunks and the
-        other ``sincos`` are right -- so the neighbouring geometries are
-        tried in the order of their expected cost (r05: first the same
+        other ``sincos`` are right -- so the neighbouring geometries
+        (``build_ladder.neighbours``) are tried in the order of their
+        expected cost (r05: first the same
         geometry with ``fast_trig=2``; strips +2, +4, +1, +6 ..., then
         ``fast_trig=1``, 16-entry chunks, then the same source through
         ``-O1`` and without the pre-RA stage of round 3), several compiled at
@@ -1934,58 +1779,23 @@ class ConstraintCollocator(object):
         used, remembered by this collocator and recorded in the plan file as
         a ``"pinned"`` entry (``__graft_entry__.build`` prebuilds those).
         Raises ``err`` when nothing passes."""
-        import copy
-        import os
-        from concurrent.futures import ThreadPoolExecutor
         from . import launch_plan
         base = self._built_options or self._printer_options()
-        geo = meta['geometry']
-        cands = []
-        # (an explicit strip count is an even cut unless the work-aware one
-        # is asked for: the neighbours of a work-aware cut are work-aware)
-        keep = dict(cut='work') if geo.get('cut') == 'work' else {}
-        if base.fast_trig != 2:
-            # first the SAME geometry with sincos behind a wave-uniform test:
-            # the one fault that is understood (profiles/r05_exec_fault.txt)
-            # sits in the if / else of the inlined library sincos, and the
-            # plan's measured geometry stays
-            cands.append(('uniform_trig', dict(fast_trig=2), {}))
-        if geo['line_mode'] or self._jacobian_layout == 'csr':
-            for d in (2, 4, 1, 6, 8, 12, -2, -4):
-                if min(geo['jac'], geo['fused']) + d >= 1:
-                    cands.append(('strips%+d' % d, dict(
-                        keep, groups=geo['jac'] + d,
-                        fused_groups=geo['fused'] + d), {}))
-        if not base.fast_trig:
-            cands.append(('fast_trig', dict(fast_trig=1), {}))
-        if geo['line_mode'] and base.chunk == 32:
-            cands.append(('chunk16', dict(chunk=16), {}))
-        cands += [('-O1', {}, dict(opt_level='-O1')),
-                  ('no-hp-reschedule', {},
-                   dict(extra_flags=list(hb.SAFE_SCHEDULER_FLAGS)))]
-
-        def build(cand):
-            label, okw, how = cand
-            opts = copy.copy(base)
-            for k, v in okw.items():
-                setattr(opts, k, v)
-            source, m = self._emit(opts)
-            hsaco = self._compile(
-                source, opt_level=how.get('opt_level'),
-                extra_flags=tuple(how.get('extra_flags', ())))
-            return label, opts, how, source, m, hsaco
-
+        trials = self._trials()
         tried = [(os.path.basename(refused), err.verdict['errors'])]
-        while cands:
-            batch, cands = cands[:4], cands[4:]
-            with ThreadPoolExecutor(len(batch)) as pool:
-                built = list(pool.map(build, batch))
-            for label, opts, how, source, m, hsaco in built:
+        for batch in bl.batches(bl.neighbours(base, meta['geometry'],
+                                              self._jacobian_layout)):
+            for (label, _, _), build in zip(
+                    batch, trials.build_all(base, batch)):
+                hsaco = build.hsaco
                 if hsaco == refused:
                     continue
-                self._built_source, self._built_options = source, opts
+                # (the referee reads the candidate's own source and options)
+                self._built_source = build.source
+                self._built_options = opts = build.options
                 try:
-                    verdict = self._verify_build(hsaco, m, force=True)
+                    verdict = self._verify_build(hsaco, build.meta,
+                                                 force=True)
                 except hb.BuildRejected as again:
                     tried.append((label, again.verdict['errors']))
                     continue
@@ -1996,13 +1806,13 @@ class ConstraintCollocator(object):
                     os.path.basename(hsaco))
                 verdict = dict(verdict, replaces=os.path.basename(refused),
                                replacement=label, refused=tried)
-                self._pinned = (opts, how)
+                self._pinned = (opts, build.how)
                 try:
                     launch_plan.record(
                         launch_plan.key_of(self._build_program(),
                                            self._launch_blocks()),
                         dict(options=launch_plan.options_kwargs(opts),
-                             pinned=dict(how, label=label,
+                             pinned=dict(build.how, label=label,
                                          replaces=os.path.basename(refused)),
                              refused=tried,
                              nodes=self._launch_nodes or
@@ -2011,7 +1821,7 @@ class ConstraintCollocator(object):
                              % (self.num_states, self._program.P)))
                 except OSError:
                     pass
-                return hsaco, m, verdict
+                return hsaco, build.meta, verdict
         raise hb.BuildRejected(
             '%s  No neighbouring build passes either: %s' % (err, tried),
             err.verdict)
@@ -2712,6 +2522,21 @@ class ConstraintCollocator(object):
         if self._hip is not None:
             return self._hip
         logger.info('Compiling the HIP constraint/Jacobian kernels.')
+        hsaco, meta = self._verified_code_object()
+        hip = hb.HipProblem(self._descriptor(meta), hsaco)
+        hip.literals = self._known_scalars() if self._specialize else None
+        self._install_tables(hip)
+        self._kernel_meta = meta
+        self._hip = hip
+        for jac, a, b in getattr(self, '_owned_outputs', ()):
+            hip.output_register(jac, a, b)
+        return hip
+
+    def _verified_code_object(self):
+        """``(hsaco, meta)`` of the build the referee accepts -- the verdict
+        is in ``_build_verdict``: :meth:`_build_code_object`'s, or, when it
+        is refused and the caller did not fix the geometry, a neighbouring
+        one (:meth:`_verified_alternative`)."""
         hsaco, meta = self._build_code_object()
         try:
             meta, self._build_verdict = self._verify_with_run_form(hsaco,
@@ -2721,14 +2546,7 @@ class ConstraintCollocator(object):
                 raise               # the caller fixed the geometry
             hsaco, meta, self._build_verdict = self._verified_alternative(
                 hsaco, meta, err)
-        hip = hb.HipProblem(self._descriptor(meta), hsaco)
-        hip.literals = self._known_scalars() if self._specialize else None
-        self._install_tables(hip)
-        self._kernel_meta = meta
-        self._hip = hip
-        for jac, a, b in getattr(self, '_owned_outputs', ()):
-            hip.output_register(jac, a, b)
-        return hip
+        return hsaco, meta
 
     def _verify_with_run_form(self, hsaco, meta):
         """``(meta, verdict)`` of :meth:`_verify_build`.  A build that the
@@ -2768,15 +2586,7 @@ class ConstraintCollocator(object):
 
     def _respecialize(self, hip):
         self._literal_values = None
-        hsaco, meta = self._build_code_object()
-        try:
-            meta, self._build_verdict = self._verify_with_run_form(hsaco,
-                                                                   meta)
-        except hb.BuildRejected as err:
-            if self._emit_options is not None or self._pinned is not None:
-                raise
-            hsaco, meta, self._build_verdict = self._verified_alternative(
-                hsaco, meta, err)
+        hsaco, meta = self._verified_code_object()
         hip.reload(self._descriptor(meta), hsaco)
         hip.literals = self._known_scalars() if self._specialize else None
         self._kernel_meta = meta
