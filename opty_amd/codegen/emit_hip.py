@@ -1010,6 +1010,60 @@ class _WavePlan(object):
         return parks, slot_of, slots, peak
 
 
+class _Kernel(object):
+    """The kernel in print: ONE record that the stages of
+    ``_ModuleWriter.kernel_record`` fill in turn and that everything below it
+    is handed; the writer keeps nothing of a kernel but its memo caches.
+    Geometry: ``order``, ``listed``, ``run``, ``publishes``, ``pub_rows``
+    (published node -> LDS row), ``rows`` / ``slab_of`` (the input slab),
+    ``ring_rows``, ``W`` waves per workgroup, ``sets`` workgroups per block.
+    Bodies: ``staged`` (trig node -> register, run form), ``park_rows``,
+    ``plans`` (one per planned wave).  LDS layout, in doubles: ``rings`` tiles
+    of ``ring`` from ``slab`` on, the published or the parking rows from
+    ``pub_base`` = ``park_base`` on, ``lds_doubles`` in all."""
+
+    def __init__(self, name, groups, con_of_group, keep, restricted, con_nt):
+        self.name, self.groups, self.con_of_group = name, groups, con_of_group
+        #: waves that are printed (all, but for the strip-dropping ablations)
+        self.keep = keep
+        self.kept = [(grp, cons) for grp, cons, k in
+                     zip(groups, con_of_group, keep) if k]
+        #: waves that stage Jacobian entries (and own a ring tile)
+        self.users = [any(e1 > e0 for e0, e1 in grp) for grp in groups]
+        #: restricted: the last strip may end inside the block and still
+        #: stage the next node's first entries
+        self.restricted, self.con_nt = bool(restricted), bool(con_nt)
+        self.pub_rows, self.staged, self.plans = {}, {}, []
+        self.park_rows = self.stage_weight = 0
+
+
+def _con_store(kn, j, ref):
+    """Store of constraint row ``j`` of the lane's node."""
+    if kn.con_nt:
+        return ('if (valid) __builtin_nontemporal_store(%s, '
+                '&con[%dLL*con_stride + node]);' % (ref, j))
+    return 'if (valid) con[%dLL*con_stride + node] = %s;' % (j, ref)
+
+
+def _switch(on, cases, pad=''):
+    """``switch (on)`` over ``[(value, lines)]``, one braced case each."""
+    out = [pad + 'switch (%s) {' % on]
+    for value, lines in cases:
+        out.append(pad + 'case %d: {' % value)
+        out += [pad + '    ' + ln for ln in lines]
+        out.append(pad + '} break;')
+    return out + [pad + 'default: break;', pad + '}']
+
+
+def _module_head(opts, what='', helpers=()):
+    """First lines of a printed module; ``helpers``: blocks it defines."""
+    return ['// generated by opty_amd.codegen.emit_hip%s -- do not edit'
+            % what, '// %s' % opts.key(),
+            '#define OPTY_STORE_AUX %d' % opts.store_aux,
+            '#include "opty_device.h"', ''] + \
+        [ln for block in helpers for ln in (block, '')]
+
+
 class _ModuleWriter(object):
 
     def __init__(self, prog, opts, inline_uniform=False, literals=None):
@@ -1032,18 +1086,9 @@ class _ModuleWriter(object):
         self._work_cut_objective = None
         self._dense = {}            # unit range -> estimated live values
         self._wcost = {}            # weighted work of entry ranges
-        self._con_nt = False        # constraint stores of the kernel in print
-        self._park_rows = 0         # LDS rows the planned waves park values in
-        self._plans = []
         self._pub = None            # publication plan (EmitOptions.publish)
-        self._pub_rows = {}         # published node -> LDS row, kernel in print
-        self._staged = {}           # staged trig node -> register, run form
 
     # -- leaves -------------------------------------------------------------
-    #: True while a restricted kernel is printed: its last strip may end
-    #: inside the block and still stage the next node's first entries
-    _restricted = False
-
     def _is_vec_input(self, i):
         return self.dag.op[i] == ir.INPUT and \
             self.dag.args[i][0] in ('cur', 'adj')
@@ -1126,14 +1171,6 @@ class _ModuleWriter(object):
     # -- grouping --------------------------------------------------------------
     def csr(self):
         return getattr(self.p, 'layout', 'coo') == 'csr'
-
-    def _row_of(self, e):
-        """Equation whose row holds stored entry ``e`` (csr layout)."""
-        rs = self.p.row_start
-        j = 0
-        while rs[j + 1] <= e:
-            j += 1
-        return j
 
     def _chunks(self, e0, e1):
         K = self.o.chunk
@@ -1521,20 +1558,20 @@ class _ModuleWriter(object):
             self._pub = (rows, tasks) if tasks else False
         return self._pub or None
 
-    def _publish_stage(self, W, slab_of):
+    def _publish_stage(self, kn):
         """Code of the stage between the slab fill and the strips: wave ``w``
         of the workgroup evaluates its share of the instances (longest
         first onto the least loaded wave) and stores their interface values
-        into the ``pub`` rows; one barrier."""
+        into the ``pub`` rows; one barrier.  ``(lines, weight)``."""
         rows, tasks = self._publication()
-        d = self.dag
+        d, W = self.dag, kn.W
         loads, mine = [0]*W, [[] for _ in range(W)]
         for iface, weight in sorted(tasks, key=lambda t: -t[1]):
             w = loads.index(min(loads))
             loads[w] += weight
             mine[w].append(iface)
-        leaf = self._leaf_fn(slab_of, {})
-        lines = ['switch (wave) {']
+        leaf = self._leaf_fn(kn, producer=True)
+        cases = []
         stored = set()
         for w in range(W):
             if not mine[w]:
@@ -1551,27 +1588,28 @@ class _ModuleWriter(object):
                         body.lines.append('pub[%d + lane] = %s;'
                                           % (rows[v]*TS, ref))
             body.end_scope()
-            lines.append('case %d: {' % w)
-            lines += ['    ' + ln for ln in body.lines]
-            lines.append('} break;')
-        lines += ['default: break;', '}', '__syncthreads();']
-        return lines, max(loads)
+            cases.append((w, body.lines))
+        return _switch('wave', cases) + ['__syncthreads();'], max(loads)
 
-    def _leaf_fn(self, slab_of, published):
-        """``leaf(i)`` of a wave's straight-line code: how a value that is
-        fetched rather than computed is fetched (input slab, node-invariant
-        table / literal / scalar home, published row), or None."""
+    def _leaf_fn(self, kn, producer=False):
+        """``leaf(i)`` of a wave's straight-line code in kernel ``kn``: how a
+        value that is fetched rather than computed is fetched (staged
+        register, published row, input slab, node-invariant table / literal
+        / scalar home), or None.  ``producer``: the code of a stage, which
+        computes what the waves find staged or published."""
         p, d = self.p, self.dag
+        staged = {} if producer else kn.staged
+        published = {} if producer else kn.pub_rows
 
         def leaf(i):
-            if i in self._staged:
-                return self._staged[i]
+            if i in staged:
+                return staged[i]
             if i in published:
                 return 'pub[%d + lane]' % (published[i]*TS)
             if self._is_vec_input(i):
                 kind, r = d.args[i]
                 off = p.cur_offset if kind == 'cur' else p.adj_offset
-                return 'lds[%d + lane + %d]' % (slab_of[r]*TS, off)
+                return 'lds[%d + lane + %d]' % (kn.slab_of[r]*TS, off)
             if self._uniform_leaf(i):
                 if i in self.literals:
                     return _lit(self.literals[i])
@@ -1590,16 +1628,23 @@ class _ModuleWriter(object):
         return leaf
 
     # -- kernels ---------------------------------------------------------------
-    def _kernel_rows(self, groups, con_of_group):
-        """Trajectory rows any wave of the kernel reads (the shared slab)."""
-        p, d = self.p, self.dag
-        roots = list(self._pub_rows)
-        for grp, cons in zip(groups, con_of_group):
+    def _wave_roots(self, waves):
+        """Outputs of the waves ``[(strips, constraint rows)]``: a strip's
+        entries and the 15 past its end that its wave evaluates as well
+        (``_virtual_end``; wrapping into the next node's), and the rows."""
+        p = self.p
+        roots = []
+        for grp, cons in waves:
             for e0, e1 in grp:
                 vend = self._virtual_end(e1) if e1 > e0 else e1
                 roots += [p.jac_out[v % p.P] for v in range(e0, vend)]
             roots += [p.con_out[j] for j in cons]
-        needed = d.reachable(roots)
+        return roots
+
+    def _kernel_rows(self, kn):
+        """Trajectory rows any wave of the kernel reads (the shared slab)."""
+        d = self.dag
+        needed = d.reachable(list(kn.pub_rows) + self._wave_roots(kn.kept))
         return sorted({d.args[i][1] for i in needed if self._is_vec_input(i)})
 
     def _ring_rows(self, grp):
@@ -1621,7 +1666,7 @@ class _ModuleWriter(object):
             return width
         return min(K, width)
 
-    def _group_body(self, grp, con_rows, slab_of):
+    def _group_body(self, kn, grp, con_rows):
         """Code for one wave evaluating the Jacobian entry strips ``grp``
         (``[(e0, e1), ...]``, in this order) and the constraint rows
         ``con_rows`` of its 64 nodes.  Inputs come from the workgroup's shared
@@ -1629,15 +1674,9 @@ class _ModuleWriter(object):
         (``ring``)."""
         p, d = self.p, self.dag
         K = self.o.chunk
-        roots = [p.con_out[j] for j in con_rows]
-        for e0, e1 in grp:
-            vend = self._virtual_end(e1) if e1 > e0 else e1
-            roots += [p.jac_out[v % p.P] for v in range(e0, vend)]
-        needed = set(d.reachable(roots))
+        needed = set(d.reachable(self._wave_roots([(grp, con_rows)])))
         R = K + 16
-
-        leaf = self._leaf_fn(slab_of, self._pub_rows)
-
+        leaf = self._leaf_fn(kn)
         body = _Body(d, needed, leaf, self.o.fast_trig,
                      self.o.deterministic, self.o.share_rcp)
         # LDS parking: the wave is planned as a whole (constraint rows
@@ -1655,15 +1694,7 @@ class _ModuleWriter(object):
             planned = est > self.o.park_live
         for j in ([] if planned else con_rows):
             body.new_scope()      # fetches hoisted per row, not per kernel
-            ref = body.emit(p.con_out[j])
-            if self._con_nt:
-                body.lines.append(
-                    'if (valid) __builtin_nontemporal_store(%s, '
-                    '&con[%dLL*con_stride + node]);' % (ref, j))
-            else:
-                body.lines.append(
-                    'if (valid) con[%dLL*con_stride + node] = %s;'
-                    % (j, ref))
+            body.lines.append(_con_store(kn, j, body.emit(p.con_out[j])))
         nv = '(N < 0 ? nvalid : 0)' if self.o.ablate == 'compute_only' \
             else 'nvalid'
 
@@ -1676,14 +1707,14 @@ class _ModuleWriter(object):
         if strips and self.line_mode():
             body.lines.append('const int b0 = opty_line_phase(jrow);')
         if strips and planned:
-            self._planned_strips(body, strips, con_rows, nv, R)
+            self._planned_strips(kn, body, strips, con_rows, nv, R)
             strips = []
         for e0, e1 in strips:
             body.lines.append('// strip %d %d' % (e0, e1))
             if self.line_mode():
-                self._strip_lines(body, e0, e1, value, nv, R)
+                self._strip_lines(kn, body, e0, e1, value, nv, R)
             elif self.csr():
-                self._strip_csr(body, e0, e1, value, nv)
+                self._strip_csr(kn, body, e0, e1, value, nv)
             elif self._whole_block_strip(grp):
                 self._strip_flat(body, value, nv)
             else:
@@ -1691,11 +1722,12 @@ class _ModuleWriter(object):
         body.end_scope()
         return body.lines
 
-    def _planned_strips(self, body, strips, con_rows, nv, R):
+    def _planned_strips(self, kn, body, strips, con_rows, nv, R):
         """The wave's code from a :class:`_WavePlan`: constraint rows and
         entry expressions in the planned order, long-lived values parked in
         the wave's LDS rows (``park``), ring writes and flushes chunk by
-        chunk in memory order."""
+        chunk in memory order.  The plan and the rows it parks in are
+        reported to ``kn``."""
         p, d = self.p, self.dag
         K = self.o.chunk
         targets = [('c', j, p.con_out[j]) for j in con_rows]
@@ -1715,11 +1747,10 @@ class _ModuleWriter(object):
 
         plan = _WavePlan(d, targets, chunks, is_leaf, self.o.park_live,
                          spread=self.o.park_spread)
-        self._park_rows = max(self._park_rows, plan.slots)
-        self._plans.append(dict(strips=strips, order=plan.order,
-                                peak=plan.peak, slots=plan.slots,
-                                ops=sum(1 for e in plan.events
-                                        if e[0] == 'op')))
+        kn.park_rows = max(kn.park_rows, plan.slots)
+        kn.plans.append(dict(strips=strips, order=plan.order,
+                            peak=plan.peak, slots=plan.slots,
+                            ops=sum(1 for e in plan.events if e[0] == 'op')))
         lines = body.lines
         reloads = [0]
 
@@ -1771,13 +1802,7 @@ class _ModuleWriter(object):
             elif ev[0] == 'con':
                 j, root = targets[ev[1]][1], targets[ev[1]][2]
                 operand(root)
-                ref = body.ref(root)
-                if self._con_nt:
-                    lines.append('if (valid) __builtin_nontemporal_store(%s, '
-                                 '&con[%dLL*con_stride + node]);' % (ref, j))
-                else:
-                    lines.append('if (valid) con[%dLL*con_stride + node] = '
-                                 '%s;' % (j, ref))
+                lines.append(_con_store(kn, j, body.ref(root)))
             else:
                 c = ev[1]
                 e0, e1, c0, c1 = flush[c]
@@ -1828,7 +1853,7 @@ class _ModuleWriter(object):
                           % (P, nv))
         body.lines.append('opty_wave_sync();')
 
-    def _strip_lines(self, body, e0, e1, value, nv, R, width=None,
+    def _strip_lines(self, kn, body, e0, e1, value, nv, R, width=None,
                      jrow='jrow', b0='b0'):
         """Ring tile + line-aligned flush of one strip (see opty_device.h).
         ``width`` doubles separate two nodes in the output (the block width P,
@@ -1836,7 +1861,7 @@ class _ModuleWriter(object):
         at the wave's first node there, ``b0`` is its line phase."""
         P = self.p.P if width is None else width
         K = self.o.chunk
-        if e1 < P and not self._restricted:
+        if e1 < P and not kn.restricted:
             assert e1 + 15 <= P, 'last entry range must be >= 16 wide'
         for c0 in range(e0, e1 + 15, K):
             c1 = min(c0 + K, e1 + 15)
@@ -1869,7 +1894,7 @@ class _ModuleWriter(object):
                                   '%d, %s, lane);' % (R, jrow, P, b0))
         body.lines.append('opty_wave_sync();')
 
-    def _strip_csr(self, body, e0, e1, value, nv):
+    def _strip_csr(self, kn, body, e0, e1, value, nv):
         """Row-sorted layout: equation j's L entries of the wave's 64 nodes
         are one contiguous span ``jac[S_j*ncn + i*L + pos]`` (``S_j`` entries
         precede row j in a block, ``ncn`` constraint nodes in this launch).
@@ -1890,16 +1915,11 @@ class _ModuleWriter(object):
                 body.lines.append('const int b0_%d = opty_line_phase(jrow%d);'
                                   % (j, j))
                 body.scope_start = len(body.lines)
-                self._strip_lines(body, 0, L, lambda v: value(S + v), nv,
+                self._strip_lines(kn, body, 0, L, lambda v: value(S + v), nv,
                                   K + 16, L, 'jrow%d' % j, 'b0_%d' % j)
                 continue
             for c0, c1 in self._chunks(S, S + L):
-                body.new_scope()
-                for e in range(c0, c1):
-                    body.begin_entry()
-                    body.lines.append('ring[%d + lane] = %s;'
-                                      % ((e - c0)*TS, value(e)))
-                body.lines.append('opty_wave_sync();')
+                self._stage_chunk(body, c0, c1, value)
                 if c0 == S and c1 == S + L:
                     body.lines.append('opty_flush_flat<%d>(ring, %s, %s, '
                                       'lane);' % (L, dst, nv))
@@ -1909,17 +1929,22 @@ class _ModuleWriter(object):
                                                       L, nv))
                 body.lines.append('opty_wave_sync();')
 
+    @staticmethod
+    def _stage_chunk(body, c0, c1, value):
+        """The chunk ``[c0, c1)`` into the tile, from its first row on."""
+        body.new_scope()
+        for e in range(c0, c1):
+            body.begin_entry()
+            body.lines.append('ring[%d + lane] = %s;'
+                              % ((e - c0)*TS, value(e)))
+        body.lines.append('opty_wave_sync();')
+
     def _strip_simple(self, body, e0, e1, value, nv):
         """Per-chunk tile + flush for tiny blocks (P < 64)."""
         p = self.p
         wide = (p.P % 2 == 0)
         for c0, c1 in self._chunks(e0, e1):
-            body.new_scope()
-            for e in range(c0, c1):
-                body.begin_entry()
-                body.lines.append('ring[%d + lane] = %s;'
-                                  % ((e - c0)*TS, value(e)))
-            body.lines.append('opty_wave_sync();')
+            self._stage_chunk(body, c0, c1, value)
             w = c1 - c0
             fl = 'opty_flush16' if (wide and w % 2 == 0 and c0 % 2 == 0) \
                 else 'opty_flush8'
@@ -1960,26 +1985,11 @@ class _ModuleWriter(object):
 
         if W == 1:
             return lines + share(0) + ['opty_wave_sync();']
-        lines.append('switch (wave) {')
-        for w in range(W):
-            lines.append('case %d: {' % w)
-            lines += ['    ' + ln for ln in share(w)]
-            lines.append('} break;')
-        lines.append('default: break;')
-        lines.append('}')
-        lines.append('__syncthreads();')
-        return lines
+        return lines + _switch('wave', [(w, share(w)) for w in range(W)]) + \
+            ['__syncthreads();']
 
-    _PROLOGUE = '''\
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long nblk = (node_end - node_begin + 63)/64;
-    // XCD-aware placement: consecutive workgroup ids round-robin the 8 XCDs;
-    // all workgroups of one 64-node block (same input slab, interleaved
-    // strips of the same output rows) go to the SAME XCD / L2, back to back.
-    const long long xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    {mapping}
-    if (blk >= nblk) return;
+    # what a wave knows of its 64 nodes (both forms of a kernel)
+    _NODE = '''\
     const long long node0 = node_begin + blk*64;
     const long long node = node0 + lane;
     const bool valid = node < node_end;
@@ -1991,6 +2001,17 @@ class _ModuleWriter(object):
     (void)valid; (void)jrow; (void)nvalid; (void)node; (void)ring; (void)grp;
     (void)ncn;
 '''
+    _PROLOGUE = '''\
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long nblk = (node_end - node_begin + 63)/64;
+    // XCD-aware placement: consecutive workgroup ids round-robin the 8 XCDs;
+    // all workgroups of one 64-node block (same input slab, interleaved
+    // strips of the same output rows) go to the SAME XCD / L2, back to back.
+    const long long xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    {mapping}
+    if (blk >= nblk) return;
+''' + _NODE
 
     # order == 'list': a persistent kernel.  At most RESIDENT_WAVES one-wave
     # workgroups (one per SIMD: these waves hold one alone), each evaluates
@@ -2050,17 +2071,7 @@ class _ModuleWriter(object):
     (void)known_traj; (void)params; (void)uni_c; (void)inst_idx; (void)con;
     (void)h; (void)con_stride;
     if (blk < nblk) {{
-    const long long node0 = node_begin + blk*64;
-    const long long node = node0 + lane;
-    const bool valid = node < node_end;
-    const long long rem = node_end - node0;
-    const int nvalid = rem < 64 ? (int)rem : 64;
-    const long long ncn = node_end - node_begin, nloc = node0 - node_begin;
-    double *jrow = jac + nloc*{P}LL;
-    double *const ring = lds + {slab} + wave*{ring};
-    (void)valid; (void)jrow; (void)nvalid; (void)node; (void)ring; (void)grp;
-    (void)ncn;
-'''
+''' + _NODE
     _LIST_NEXT = '''\
     }
     }
@@ -2069,83 +2080,120 @@ class _ModuleWriter(object):
     }
 '''
 
-    def _trig_stage(self, groups, con_of_group, slab_of):
-        """Run form of the restricted kernels: ``(registers, lines)`` of the
-        block's trig stage -- every sin / cos node any wave of the kernel
-        needs whose argument is a slab value, evaluated once per block into
-        registers declared outside the item loop (``{node: name}``)."""
-        p, d = self.p, self.dag
-        roots = []
-        for grp, cons in zip(groups, con_of_group):
-            for e0, e1 in grp:
-                vend = self._virtual_end(e1) if e1 > e0 else e1
-                roots += [p.jac_out[v % p.P] for v in range(e0, vend)]
-            roots += [p.con_out[j] for j in cons]
-        needed = set(d.reachable(roots))
+    def _trig_stage(self, kn):
+        """Run form of the restricted kernels: the lines of the block's trig
+        stage -- every sin / cos node any wave of the kernel needs whose
+        argument is a slab value, evaluated once per block into registers
+        declared outside the item loop (``kn.staged``: ``{node: name}``)."""
+        d = self.dag
+        needed = set(d.reachable(self._wave_roots(kn.kept)))
         nodes = sorted(i for i in needed if d.op[i] in ('sin', 'cos') and
                        self._is_vec_input(d.args[i][0]))
-        body = _Body(d, set(nodes), self._leaf_fn(slab_of, {}),
+        body = _Body(d, set(nodes), self._leaf_fn(kn, producer=True),
                      self.o.fast_trig, self.o.deterministic)
         body.new_scope()
-        regs = {}
         for i in nodes:
-            regs[i] = 'tg%d' % i
-            body.lines.append('%s = %s;' % (regs[i], body.emit(i)))
+            kn.staged[i] = 'tg%d' % i
+            body.lines.append('%s = %s;' % (kn.staged[i], body.emit(i)))
         body.end_scope()
-        return regs, body.lines
+        return body.lines
 
-    def kernel(self, name, groups, con_of_group, W=1, con_nt=False,
-               inst_lines=None, first_group=0, order=None, run=0):
-        """One kernel.  ``groups`` = one list of entry strips ``(e0, e1)`` per
-        wave; ``con_of_group[g]`` = constraint rows stored by wave g.  A
-        workgroup is ``W`` consecutive groups of one 64-node block: they share
-        one input slab (filled cooperatively) and each owns a ring tile.
-        ``run``: > 0 = the run form of a restricted kernel
+    def kernel(self, *args, **kwargs):
+        """``(text, meta)`` of one kernel (arguments: ``kernel_record``)."""
+        kn = self.kernel_record(*args, **kwargs)
+        return kn.text, kn.meta
+
+    def kernel_record(self, name, groups, con_of_group, W=1, con_nt=False,
+                      inst_lines=None, first_group=0, order=None, run=0,
+                      restricted=False):
+        """Prints one kernel, stage by stage; returns its :class:`_Kernel`
+        with ``text`` and ``meta``.  ``groups`` = one list of entry strips
+        ``(e0, e1)`` per wave; ``con_of_group[g]`` = constraint rows stored
+        by wave g.  A workgroup is ``W`` consecutive groups of one 64-node
+        block: they share one input slab (filled cooperatively) and each
+        owns a ring tile.  ``restricted``: a restricted kernel (strips inside
+        the kept spans); ``run``: > 0 = its run form
         (``EmitOptions.var_order``) with at most that many workgroups.
         ``inst_lines``: body of the instance-constraint tails, run by lane 0
         of the first workgroup AFTER the node blocks' (the runtime launches
         it only with whole-problem evaluations).  ``first_group``: the
         workgroup of a block that holds this wave is dispatched first, the
         others follow cyclically."""
-        G = len(groups)
-        self._con_nt = bool(con_nt)
-        keep = [True]*G
-        if self.o.ablate in ('only_cheap', 'only_dear'):
-            cheap = [sum(self._strip_cost(*rg) for rg in grp if rg[1] > rg[0])
-                     <= 16 and not con_of_group[g]
-                     for g, grp in enumerate(groups)]
-            keep = [c == (self.o.ablate == 'only_cheap') for c in cheap]
+        kn = _Kernel(name, groups, con_of_group,
+                    self._keep(groups, con_of_group), restricted, con_nt)
+        self._geometry(kn, W, order, run)
+        # (the bodies fill ``kn.staged``, ``kn.park_rows``, ``kn.plans``)
+        stage = self._trig_stage(kn) if kn.run else []
+        bodies = [self._group_body(kn, grp, con_of_group[g]) if kn.keep[g]
+                  else [] for g, grp in enumerate(groups)]
+        self._lds_layout(kn)
+        head, tail, stamp = self._trace(kn)
+        src = self._signature(kn) + self._instance_tail(kn, inst_lines)
+        if kn.listed:
+            # one loop around the switch: items in the order of the schedule
+            src += self._item_loop(kn)
+        else:
+            src += [self._PROLOGUE.format(
+                P=self.p.P, mapping=self._mapping(kn, first_group),
+                slab=kn.slab, ring=kn.ring)]
+        if kn.park_rows and not kn.listed:
+            # the wave's parking rows (behind the ring tiles); reloads go
+            # through ``lane_z`` == lane, which the compiler cannot prove, so
+            # that it neither forwards the parked value from its register
+            # (which would keep it alive) nor moves a reload above its store
+            src += ['    double *const park = lds + %d + wave*%d;'
+                    % (kn.park_base, kn.park_rows*WAVE),
+                    '    const int lane_z = lane + (int)(N >> 62);']
+        src += head + self._fill(kn, stage, stamp)
+        if len(groups) == 1 and not kn.listed:
+            src += ['    ' + ln for ln in bodies[0]]
+        else:
+            src += _switch('grp', enumerate(bodies), '    ')
+        src += tail + ([self._LIST_NEXT] if kn.listed else []) + ['}']
+        kn.text = '\n'.join(src)
+        kn.meta = self._kernel_meta(kn)
+        return kn
+
+    # -- geometry: what is decided before any text ----------------------------
+    def _keep(self, groups, con_of_group):
+        if self.o.ablate not in ('only_cheap', 'only_dear'):
+            return [True]*len(groups)
+        cheap = [sum(self._strip_cost(*rg) for rg in grp if rg[1] > rg[0])
+                 <= 16 and not con_of_group[g]
+                 for g, grp in enumerate(groups)]
+        return [c == (self.o.ablate == 'only_cheap') for c in cheap]
+
+    def _geometry(self, kn, W, order, run):
+        o, G = self.o, len(kn.groups)
+        kn.order = order or o.order
+        kn.listed = bool((kn.order == 'list' or run) and G <= MAX_CLASSES and
+                         any(kn.users))
+        kn.run = run if kn.listed else 0
         # publication of the block's isomorphic sub-models (one workgroup
         # per block, a stage and a barrier before the strips): Jacobian
         # kernels of line-mode blocks with several waves, hardware dispatch
-        self._pub_rows = {}
         pub = None
-        if self.o.publish and name in ('opty_jac', 'opty_conjac') and \
-                G > 1 and G <= 16 and self.line_mode() and \
-                (order or self.o.order) != 'list' and not self.o.park and \
-                self.o.ablate is None and not self.o.trace:
+        if o.publish and kn.name in ('opty_jac', 'opty_conjac') and \
+                1 < G <= 16 and self.line_mode() and kn.order != 'list' and \
+                not o.park and o.ablate is None and not o.trace:
             pub = self._publication()
-        if pub is not None:
-            self._pub_rows = pub[0]
-        rows = self._kernel_rows([g for g, k in zip(groups, keep) if k],
-                                 [c for c, k in zip(con_of_group, keep) if k])
-        ring_rows = max([self._ring_rows(g) for g in groups] + [0])
-        if pub is not None:
-            nring = sum(any(e1 > e0 for e0, e1 in grp) for grp in groups)
-            if (len(rows) + nring*ring_rows + len(pub[0]))*TS*8 > 160*1024:
-                # does not fit a CU's LDS next to the ring tiles
-                pub, self._pub_rows = None, {}
-                rows = self._kernel_rows(
-                    [g for g, k in zip(groups, keep) if k],
-                    [c for c, k in zip(con_of_group, keep) if k])
-            else:
-                W = G
-        slab_of = {r: k for k, r in enumerate(rows)}
+        kn.pub_rows = pub[0] if pub else {}
+        kn.rows = self._kernel_rows(kn)
+        kn.ring_rows = max([self._ring_rows(g) for g in kn.groups] + [0])
+        if pub and (len(kn.rows) + sum(kn.users)*kn.ring_rows +
+                    len(pub[0]))*TS*8 > 160*1024:
+            # does not fit a CU's LDS next to the ring tiles
+            pub, kn.pub_rows = None, {}
+            kn.rows = self._kernel_rows(kn)
+        kn.publishes = pub is not None
+        if kn.publishes:
+            W = G
+        kn.slab_of = {r: i for i, r in enumerate(kn.rows)}
         if W is None:
-            if G <= 4 and any(con_of_group) and not self.o.strips and \
-                    not self.o.fused_strips and \
-                    self.o.cut != 'work' and self._auto_work is None and \
-                    any(e1 > e0 for grp in groups for e0, e1 in grp):
+            if G <= 4 and any(kn.con_of_group) and not o.strips and \
+                    not o.fused_strips and \
+                    o.cut != 'work' and self._auto_work is None and \
+                    any(kn.users):
                 # the fused kernel of a small block: its few waves form ONE
                 # workgroup -- one slab fill, and the constraint wave rides in
                 # the Jacobian wave's LDS instead of reserving a ring tile it
@@ -2154,65 +2202,63 @@ class _ModuleWriter(object):
                 # until its longest wave is done.)
                 W = G
             else:
-                W = self._waves_per_workgroup(len(rows), ring_rows)
-        W = max(1, min(W, G))
-        order = order or self.o.order
-        listed = (order == 'list' or run) and G <= MAX_CLASSES and any(
-            e1 > e0 for grp in groups for e0, e1 in grp)
-        run = run if listed else 0
-        if listed:
-            W = 1
+                W = self._waves_per_workgroup(len(kn.rows), kn.ring_rows)
+        W = 1 if kn.listed else max(1, min(W, G))
         # a hand-set workgroup width that does not fit the CU's LDS (64-entry
         # chunks of a 4-wave workgroup next to a large slab) is narrowed
         # instead of failing in hipcc ("local memory exceeds limit")
-        while W > 1 and (len(rows) + W*ring_rows)*TS*8 > 160*1024:
+        while W > 1 and (len(kn.rows) + W*kn.ring_rows)*TS*8 > 160*1024:
             W -= 1
-        sets = (G + W - 1)//W
-        self._park_rows = 0
-        stage = []
-        if run:
-            # (set while the waves' code is printed: their trig leaves)
-            self._staged, stage = self._trig_stage(
-                [g for g, k in zip(groups, keep) if k],
-                [c for c, k in zip(con_of_group, keep) if k], slab_of)
-        bodies = [self._group_body(grp, con_of_group[g], slab_of)
-                  if keep[g] else []
-                  for g, grp in enumerate(groups)]
-        staged, self._staged = self._staged, {}
-        park_rows = self._park_rows
-        self.uses_park = getattr(self, 'uses_park', False) or park_rows > 0
+        kn.W, kn.sets = W, (G + W - 1)//W
+        # what cannot be: the run form comes with neither publication nor
+        # parking (``restricted_ranges``); a publishing kernel is one
+        # workgroup per block, dispatched by the hardware, and parks nothing
+        assert not (kn.run and (kn.publishes or o.park))
+        assert not kn.publishes or (W == G and not kn.listed and not o.park)
+
+    def _lds_layout(self, kn):
         # Ring tiles only for the waves that stage Jacobian entries: the
         # constraint waves come last, so in every workgroup the ring users
         # are its first waves (tile index == wave index) and a workgroup of
         # [Jacobian wave, constraint wave] -- the fused kernel of a small
         # block -- holds one tile, not two.
-        users = [any(e1 > e0 for e0, e1 in grp) for grp in groups]
-        rings = 0
-        for w0 in range(0, G, W):
-            mine = users[w0:w0 + W]
+        kn.rings = 0
+        for w0 in range(0, len(kn.users), kn.W):
+            mine = kn.users[w0:w0 + kn.W]
             assert mine == sorted(mine, reverse=True), 'ring users first'
-            rings = max(rings, sum(mine))
-        if W == 1:
-            rings = 1           # one size per kernel: nothing to share
-        pub_base = (len(rows) + rings*ring_rows)*TS
-        lds_doubles = max(1, pub_base + len(self._pub_rows)*TS +
-                          W*park_rows*WAVE)
+            kn.rings = max(kn.rings, sum(mine))
+        if kn.W == 1:
+            kn.rings = 1        # one size per kernel: nothing to share
+        kn.slab, kn.ring = len(kn.rows)*TS, kn.ring_rows*TS
+        kn.pub_base = kn.park_base = kn.slab + kn.rings*kn.ring
+        kn.lds_doubles = max(1, kn.pub_base + len(kn.pub_rows)*TS +
+                             kn.W*kn.park_rows*WAVE)
+
+    # -- text -----------------------------------------------------------------
+    def _signature(self, kn):
         occ = ' __attribute__((amdgpu_waves_per_eu(%d, %d)))' % (
             self.o.occupancy, self.o.occupancy) if self.o.occupancy else ''
-        src = ['extern "C" __global__ void __launch_bounds__(%d)%s'
-               % (64*W, occ),
-               '%s(%s)' % (name, KERNEL_PARAMS + (
-                   ', const int *__restrict__ sched' if listed else '')), '{',
-               '    __shared__ double lds[%d];' % lds_doubles]
-        if listed:
-            src += [self._LIST_HEAD]
-        if inst_lines:
-            src += ['    if (blockIdx.x >= npw) {' if listed else
-                    '    if (blockIdx.x >= ((node_end - node_begin + 63)/64 + '
-                    '7)/8*8*%d) {' % sets,
-                    '        if (threadIdx.x == 0) {']
-            src += ['            ' + ln for ln in inst_lines]
-            src += ['        }', '        return;', '    }']
+        return ['extern "C" __global__ void __launch_bounds__(%d)%s'
+                % (64*kn.W, occ),
+                '%s(%s)' % (kn.name, KERNEL_PARAMS + (
+                    ', const int *__restrict__ sched' if kn.listed else '')),
+                '{', '    __shared__ double lds[%d];' % kn.lds_doubles] + \
+            ([self._LIST_HEAD] if kn.listed else [])
+
+    def _instance_tail(self, kn, inst_lines):
+        """The workgroup behind the node blocks' evaluates the folded tails."""
+        if not inst_lines:
+            return []
+        return ['    if (blockIdx.x >= npw) {' if kn.listed else
+                '    if (blockIdx.x >= ((node_end - node_begin + 63)/64 + '
+                '7)/8*8*%d) {' % kn.sets,
+                '        if (threadIdx.x == 0) {'] + \
+            ['            ' + ln for ln in inst_lines] + \
+            ['        }', '        return;', '    }']
+
+    def _mapping(self, kn, first_group):
+        """Hardware dispatch: ``blk`` and ``grp`` of a workgroup's slot."""
+        W, sets = kn.W, kn.sets
         rot = 'slot' if (first_group//W) % sets == 0 else \
             '(slot + %d)' % ((first_group//W) % sets)
         rotate = self.o.rotate
@@ -2227,11 +2273,11 @@ class _ModuleWriter(object):
             # biped's Jacobian kernel with 4 work-aware strips: 0.104 ms,
             # with 5: 0.066 ms).
             rot = '(%s + slot/%d)' % (rot, sets)
-        if order == 'tail' and sets > 1:
+        if kn.order == 'tail' and sets > 1:
             # block by block, then the last ``tail`` blocks of every XCD
             # class by class (sets sorted longest first)
             tail = max(1, RESIDENT_WAVES//(8*max(1, sets - 1)))
-            mapping = (
+            return (
                 'const long long nslot = (nblk + 7) >> 3;\n'
                 '    const long long ntail = nslot < {tail} ? nslot : {tail};\n'
                 '    const long long nhead = nslot - ntail;\n'
@@ -2240,147 +2286,112 @@ class _ModuleWriter(object):
                 'nhead + stail % ntail)*8 + xcd;\n'
                 '    const int grp = (int)(stail < 0 ? slot % {sets} : '
                 'stail/ntail)*{W} + wave;').format(W=W, sets=sets, tail=tail)
-        elif order in ('class', 'tail'):
+        if kn.order in ('class', 'tail'):
             # strip class by strip class: workgroup set s of every block
             # before set s + 1 of any (the printer sorted the sets longest
             # first); a block's workgroups stay on one XCD
-            mapping = ('const long long nslot = (nblk + 7) >> 3;\n'
-                       '    const long long blk = (slot % nslot)*8 + xcd;\n'
-                       '    const int grp = (int)(slot/nslot)*{W} + wave;'
-                       ).format(W=W)
-        else:
-            mapping = ('const long long blk = (slot/{sets})*8 + xcd;\n'
-                       '    const int grp = (int)({rot} % {sets})*{W} + wave;'
-                       ).format(sets=sets, W=W, rot=rot)
-        if not listed:
-            src += [self._PROLOGUE.format(P=self.p.P, mapping=mapping,
-                                          slab=len(rows)*TS,
-                                          ring=ring_rows*TS)]
-        if park_rows and listed:
-            src.append('    double *const park_o = lds + %d;'
-                       % ((len(rows) + rings*ring_rows)*TS))
-        elif park_rows:
-            # the wave's parking rows (behind the ring tiles); reloads go
-            # through ``lane_z`` == lane, which the compiler cannot prove, so
-            # that it neither forwards the parked value from its register
-            # (which would keep it alive) nor moves a reload above its store
-            src += ['    double *const park = lds + %d + wave*%d;'
-                    % ((len(rows) + rings*ring_rows)*TS, park_rows*WAVE),
-                    '    const int lane_z = lane + (int)(N >> 62);']
-        trace_head = [
-            '    const long long tr_w0 = wall_clock64();',
-            '    const long long tr_c0 = __builtin_readcyclecounter();'] \
-            if self.o.trace else []
-        trace_tail = [
+            return ('const long long nslot = (nblk + 7) >> 3;\n'
+                    '    const long long blk = (slot % nslot)*8 + xcd;\n'
+                    '    const int grp = (int)(slot/nslot)*{W} + wave;'
+                    ).format(W=W)
+        return ('const long long blk = (slot/{sets})*8 + xcd;\n'
+                '    const int grp = (int)({rot} % {sets})*{W} + wave;'
+                ).format(sets=sets, W=W, rot=rot)
+
+    def _item_loop(self, kn):
+        """Listed form: from the kernel's head to an item's own code."""
+        src = ['    double *const park_o = lds + %d;' % kn.park_base] \
+            if kn.park_rows else []
+        if kn.run:
+            src += ['    long long blk_prev = -1;'] + [
+                '    double %s = 0.0;' % r for r in sorted(kn.staged.values())]
+        src += [self._LIST_LOOP,
+                self._LIST_ITEM.format(P=self.p.P, slab=kn.slab, ring=kn.ring)]
+        if kn.park_rows:
+            src += ['    double *const park = park_o;',
+                    '    const int lane_z = lane + (int)(N >> 62);',
+                    '    (void)park; (void)lane_z;']
+        return src
+
+    def _trace(self, kn):
+        """``(head, tail, stamp)`` of ``EmitOptions.trace``: the wave's start,
+        its record, and -- restricted kernels -- the end of its fill."""
+        if not self.o.trace:
+            return [], [], []
+        head = ['    const long long tr_w0 = wall_clock64();',
+                '    const long long tr_c0 = __builtin_readcyclecounter();']
+        stamp = []
+        if kn.restricted:
+            # the stamp waits for the last value the fill (the stage) loaded
+            # (computed): the loads return in order
+            last = sorted(kn.staged.values()) or (
+                ['sl%d' % kn.rows[-1]] if kn.W == 1 and kn.rows else [])
+            stamp = ['    asm volatile("" :: "v"(%s));' % v for v in last]
+            stamp.append('    tr_w1 = wall_clock64();')
+            head.append('    long long tr_w1 = tr_w0;')
+        tail = [
             '    if (lane == 0 && jac) {',
             '        long long *tr = reinterpret_cast<long long *>(jac + '
             'ncn*%dLL + %d) + ((long long)%s*%d + wave)*4;'
             % (self.p.P, TRACE_OFFSET,
-               '(((long long)(item & 0xffffff)*%d + grp)*8 + xcd)' % sets
-               if listed else 'blockIdx.x', W),
+               '(((long long)(item & 0xffffff)*%d + grp)*8 + xcd)' % kn.sets
+               if kn.listed else 'blockIdx.x', kn.W),
             '        tr[0] = tr_w0; tr[1] = wall_clock64();',
             '        tr[2] = ((long long)grp << 40) | %sblk;' % (
                 # restricted kernels: wall-clock ticks (at most 65535) from
                 # the wave's / item's start to the end of its slab fill (run
                 # form: and trig stage; 0 on an item that needed neither)
                 '((tr_w1 - tr_w0 > 65535 ? 65535LL : tr_w1 - tr_w0) << 24) | '
-                if self._restricted else ''),
+                if kn.restricted else ''),
             '        tr[3] = ((long long)(__builtin_readcyclecounter() - '
             'tr_c0) << 24) | (long long)(__builtin_amdgcn_s_getreg('
             'GETREG_IMMED(3, 0, 20)) << 16) | (long long)'
             '__builtin_amdgcn_s_getreg(GETREG_IMMED(15, 0, 4));',
-            '    }'] if self.o.trace else []
-        fill = ['    ' + ln for ln in self._slab_fill(rows, slab_of, W)]
-        if self.o.trace and self._restricted:
-            # the stamp waits for the last value the fill (the stage) loaded
-            # (computed): the loads return in order
-            last = sorted(staged.values()) or (
-                ['sl%d' % rows[-1]] if W == 1 and rows else [])
-            stamp = ['    asm volatile("" :: "v"(%s));' % v for v in last]
-            stamp.append('    tr_w1 = wall_clock64();')
-        else:
-            stamp = []
-        if run:
-            # the slab and the trig stage, only when the block changes
+            '    }']
+        return head, tail, stamp
+
+    def _fill(self, kn, stage, stamp):
+        """Slab fill (run form: and trig stage, on a new block), publication."""
+        fill = ['    ' + ln
+                for ln in self._slab_fill(kn.rows, kn.slab_of, kn.W)]
+        if kn.run:
             fill = (['    if (blk != blk_prev) {'] + fill +
                     ['    ' + ln for ln in stage] + stamp +
                     ['    blk_prev = blk;', '    }'])
         else:
             fill += stamp
-        if stamp:
-            trace_head.append('    long long tr_w1 = tr_w0;')
-        stage_weight = 0
-        if pub is not None:
-            assert W == G and not listed and not park_rows
-            stage, stage_weight = self._publish_stage(W, slab_of)
-            fill += ['    double *const pub = lds + %d;' % pub_base] + \
+        if kn.publishes:
+            stage, kn.stage_weight = self._publish_stage(kn)
+            fill += ['    double *const pub = lds + %d;' % kn.pub_base] + \
                 ['    ' + ln for ln in stage]
-        if listed:
-            # one loop around the switch: items in the order of the schedule
-            if run:
-                src += ['    long long blk_prev = -1;'] + [
-                    '    double %s = 0.0;' % r
-                    for r in sorted(staged.values())]
-            src += [self._LIST_LOOP,
-                    self._LIST_ITEM.format(P=self.p.P, slab=len(rows)*TS,
-                                           ring=ring_rows*TS)]
-            if park_rows:
-                src += ['    double *const park = park_o;',
-                        '    const int lane_z = lane + (int)(N >> 62);',
-                        '    (void)park; (void)lane_z;']
-            src += trace_head + fill
-            src.append('    switch (grp) {')
-            for g, lines in enumerate(bodies):
-                src.append('    case %d: {' % g)
-                src += ['        ' + ln for ln in lines]
-                src.append('    } break;')
-            src.append('    default: break;')
-            src.append('    }')
-            src += trace_tail + [self._LIST_NEXT]
-        else:
-            src += trace_head + fill
-            if G == 1:
-                src += ['    ' + ln for ln in bodies[0]]
-            else:
-                src.append('    switch (grp) {')
-                for g, lines in enumerate(bodies):
-                    src.append('    case %d: {' % g)
-                    src += ['        ' + ln for ln in lines]
-                    src.append('    } break;')
-                src.append('    default: break;')
-                src.append('    }')
-            src += trace_tail
-        src.append('}')
-        text = '\n'.join(src)
-        # sha of this kernel's own source: profiles/traffic.json keys the PMC
-        # counters on it, so that they go stale with the kernel they were
-        # collected on and not with a change elsewhere in the module
-        return text, dict(name=name, groups=G, waves_per_wg=W,
-                          wgs_per_block=sets, lds_bytes=lds_doubles*8,
-                          park_rows=park_rows,
-                          published_rows=len(self._pub_rows),
-                          publish_stage_weight=stage_weight,
-                          # (``persist``: the workgroups of a LIST schedule;
-                          # a run schedule's are ``run_persist``)
-                          persist=RESIDENT_WAVES if listed and not run else 0,
-                          run_persist=run,
-                          class_cost=(None if run else
-                                      self._given_cost(name, G)) or [
-                              float(sum(self._weighted_cost(e0, e1) +
-                                        STORE_WEIGHT*(e1 - e0)
-                                        for e0, e1 in grp if e1 > e0) +
-                                    60*len(con_of_group[g]) + 100)
-                              for g, grp in enumerate(groups)]
-                          if listed else [],
-                          sha=hashlib.sha256(text.encode()).hexdigest())
+        return fill
 
-    def _given_cost(self, name, G):
-        given = self.o.fused_class_cost if name == 'opty_conjac' \
-            else self.o.class_cost
-        if not given:
-            return None
-        cost = [float(c) for c in str(given).split(';')]
-        return cost if len(cost) == G else None
+    def _kernel_meta(self, kn):
+        G, cost = len(kn.groups), []
+        if kn.listed:
+            # relative wave durations of the strip classes: as measured
+            # (a list schedule's ``class_cost``), else the printer's estimate
+            given = self.o.fused_class_cost if kn.name == 'opty_conjac' \
+                else self.o.class_cost
+            cost = [float(c) for c in str(given).split(';')] \
+                if given and not kn.run else []
+            if len(cost) != G:
+                cost = [float(sum(self._weighted_cost(e0, e1) +
+                                  STORE_WEIGHT*(e1 - e0)
+                                  for e0, e1 in grp if e1 > e0) +
+                              60*len(kn.con_of_group[g]) + 100)
+                        for g, grp in enumerate(kn.groups)]
+        # ``persist``: the workgroups of a LIST schedule (a run schedule's are
+        # ``run_persist``); ``sha`` of this kernel's own source: profiles/
+        # traffic.json keys the PMC counters on it, so that they go stale with
+        # the kernel they were collected on, not with a change elsewhere
+        return dict(name=kn.name, groups=G, waves_per_wg=kn.W,
+                    wgs_per_block=kn.sets, lds_bytes=kn.lds_doubles*8,
+                    park_rows=kn.park_rows, published_rows=len(kn.pub_rows),
+                    publish_stage_weight=kn.stage_weight,
+                    persist=RESIDENT_WAVES if kn.listed and not kn.run else 0,
+                    run_persist=kn.run, class_cost=cost,
+                    sha=hashlib.sha256(kn.text.encode()).hexdigest())
 
     @staticmethod
     def _waves_per_workgroup(slab_rows, ring_rows, lds_per_cu=160*1024):
@@ -2399,17 +2410,16 @@ class _ModuleWriter(object):
                 best, best_w = waves, W
         return best_w
 
+    def _scalar_leaf(self, i):
+        """``leaf(i)`` of one-lane code: scalar inputs from their homes."""
+        return self._scalar_source(i) if self.dag.op[i] == ir.INPUT else None
+
     def uniform_kernel(self):
         """Must be printed after every kernel that allocates ``uni`` slots."""
         d = self.dag
         slots = sorted(self.uni_slot.items(), key=lambda kv: kv[1])
         roots = [i for i, _ in slots]
         needed = set(d.reachable(roots))
-
-        def leaf(i):
-            if d.op[i] == ir.INPUT:
-                return self._scalar_source(i)
-            return None
 
         # The table is filled by up to UNI_WORKGROUPS single-lane workgroups
         # (problems whose table depends on `free` -- variable duration,
@@ -2419,20 +2429,19 @@ class _ModuleWriter(object):
         nparts = max(1, min(UNI_WORKGROUPS, len(slots)//48))
         src = ['extern "C" __global__ void __launch_bounds__(64)',
                'opty_uni(%s)' % KERNEL_PARAMS, '{',
-               '    if (threadIdx.x != 0) return;',
-               '    switch (blockIdx.x) {']
+               '    if (threadIdx.x != 0) return;']
+        cases = []
         for b in range(nparts):
             part = slots[b*len(slots)//nparts:(b + 1)*len(slots)//nparts]
-            body = _Body(d, set(d.reachable([i for i, _ in part])), leaf,
-                         self.o.fast_trig, self.o.deterministic)
+            body = _Body(d, set(d.reachable([i for i, _ in part])),
+                         self._scalar_leaf, self.o.fast_trig,
+                         self.o.deterministic)
             for i, s in part:
                 ref = body.emit(i)
                 body.lines.append('uni_w[%d] = %s;' % (s, ref))
             body.end_scope()
-            src.append('    case %d: {' % b)
-            src += ['        ' + ln for ln in body.lines]
-            src.append('    } break;')
-        src += ['    default: break;', '    }', '}']
+            cases.append((b, body.lines))
+        src += _switch('blockIdx.x', cases, '    ') + ['}']
         dynamic = any(d.op[i] == ir.INPUT and
                       self._scalar_source(i).startswith('free_')
                       for i in needed)
@@ -2446,12 +2455,7 @@ class _ModuleWriter(object):
         roots = list(p.inst_con_out) + list(p.inst_jac_out)
         needed = set(d.reachable(roots))
 
-        def leaf(i):
-            if d.op[i] == ir.INPUT:
-                return self._scalar_source(i)
-            return None
-
-        body = _Body(d, needed, leaf, self.o.fast_trig,
+        body = _Body(d, needed, self._scalar_leaf, self.o.fast_trig,
                      self.o.deterministic)
         for k, node in enumerate(p.inst_con_out):
             ref = body.emit(node)
@@ -2713,15 +2717,62 @@ def emit_matrix_module(prog, opts=None):
                           opts.waves)
     usrc, num_uniform, dynamic = w.uniform_kernel()
     assert not dynamic
-    head = ['// generated by opty_amd.codegen.emit_hip (matrix program) -- '
-            'do not edit', '// %s' % opts.key(),
-            '#define OPTY_STORE_AUX %d' % opts.store_aux,
-            '#include "opty_device.h"', '']
-    source = '\n'.join(head + [src, '', usrc, ''])
+    source = '\n'.join(_module_head(opts, ' (matrix program)') +
+                       [src, '', usrc, ''])
     meta = dict(kernels={'jac': kmeta}, chunk=opts.chunk, P=prog.P,
                 num_uniform=num_uniform, uniform_dynamic=False,
                 sha=hashlib.sha256(source.encode()).hexdigest())
     return source, meta
+
+
+def _restricted_section(prog, w, opts, groups, fused_jac, detached_sets,
+                        nt_fused, folded):
+    """The restricted flavour of the two Jacobian kernels, for outputs whose
+    owner keeps them between evaluations (opty_hip_output_register): only
+    the lines that hold an entry which can change are written, the strips
+    are cut inside the kept spans; the entries' code is the full kernels'.
+    The constraint rows ride in waves of their own.  Returns
+    ``meta['restricted']`` (or None) and ``(parts, kernels)`` of the dispatch
+    form and of the run form (a code object of its own: ``meta['run']``)."""
+    var_ranges = w.restricted_ranges()
+    out = ([], {}), ([], {})
+    if not var_ranges:
+        return (None,) + out
+    # (rounded up: a restricted strip is never wider than a full one, whose
+    # register budget it shares)
+    share = sum(hi - lo for lo, hi in var_ranges)/float(prog.P)
+    var_groups = w.restricted_strips(
+        var_ranges, opts.var_groups if opts.var_groups is not None
+        else int(math.ceil(len(groups)*share)))
+    var_fused = w.restricted_strips(
+        var_ranges, opts.var_fused_groups
+        if opts.var_fused_groups is not None
+        else int(math.ceil(len(fused_jac)*share)))
+    forms = (0, opts.var_persist) if opts.var_order == 'run' else (0,)
+    for key, name, grp, cons, nt in (
+            ('jac_var', 'opty_jac_var', var_groups,
+             [[] for _ in var_groups], False),
+            ('conjac_var', 'opty_conjac_var',
+             list(var_fused) + [[(0, 0)]]*len(detached_sets),
+             [[] for _ in var_fused] + detached_sets, nt_fused)):
+        # ... and, for a code object of its own, the run form of the same
+        # kernel: this module, and with it the full kernels' code, stays
+        # what it is without the form.  Printed by the same writer right
+        # behind the dispatch form: the node-invariant values it reads have
+        # their table slots
+        for (parts, kernels), run in zip(out, forms):
+            nslots = len(w.uni_slot)
+            src, meta = w.kernel(name, grp, cons, opts.waves, nt,
+                                 inst_lines=folded, order='block', run=run,
+                                 restricted=True)
+            assert not run or len(w.uni_slot) == nslots
+            meta['order'] = 'run' if meta['run_persist'] else 'dispatch'
+            parts += [src, '']
+            kernels[key] = meta
+    return (dict(
+        owner_ranges=[list(rg) for rg in var_ranges],
+        groups=[[list(rg) for rg in grp] for grp in var_groups],
+        fused_groups=[[list(rg) for rg in grp] for grp in var_fused]),) + out
 
 
 def emit_module(prog, opts=None, node_blocks=None, literals=None):
@@ -2849,11 +2900,9 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
     detached_sets = con_sets
     attached, con_sets = _attach_constraint_rows(prog, w, opts, fused_jac,
                                                  con_sets)
-    con_groups = [[(0, 0)]]*len(con_sets)
-    fused_groups = list(fused_jac) + con_groups
+    fused_groups = list(fused_jac) + [[(0, 0)]]*len(con_sets)
     con_of = attached + con_sets
-    parts = []
-    kernels = {}
+    parts, kernels, plans = [], {}, []
     # Constraint stores.  Written once, never re-read by the kernels: on their
     # own (opty_con) they are fastest streamed past the caches (10-link,
     # N = 10^5: 0.0118 vs 0.0137 ms).  In the fused kernel a constraint vector
@@ -2883,90 +2932,30 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
              [[] for _ in range(len(groups) + opts.pad)], opts.waves, False),
             ('conjac', 'opty_conjac', fused_groups, con_of, opts.waves,
              nt_fused)):
-        src, meta = w.kernel(
+        kn = w.kernel_record(
             name, grp, cons, wpw, nt, inst_lines=folded,
             first_group=len(fused_jac) if (opts.dear_first and
                                            key == 'conjac') else 0,
             order=opts.fused_order if key == 'conjac' else None)
-        parts += [src, '']
-        kernels[key] = meta
-    # The restricted flavour of the two Jacobian kernels, for outputs whose
-    # owner keeps them between evaluations (opty_hip_output_register): only
-    # the lines that hold an entry which can change are written, the strips
-    # are cut inside the kept spans; the entries' code is the full kernels'.
-    # The constraint rows ride in waves of their own.
-    var_ranges = w.restricted_ranges()
-    var_groups = var_fused = None
-    run_parts, run_kernels = [], {}
-    if var_ranges:
-        # (rounded up: a restricted strip is never wider than a full one,
-        # whose register budget it shares)
-        share = sum(hi - lo for lo, hi in var_ranges)/float(prog.P)
-        var_groups = w.restricted_strips(
-            var_ranges, opts.var_groups if opts.var_groups is not None
-            else int(math.ceil(len(groups)*share)))
-        var_fused = w.restricted_strips(
-            var_ranges, opts.var_fused_groups
-            if opts.var_fused_groups is not None
-            else int(math.ceil(len(fused_jac)*share)))
-        w._restricted = True
-        for key, name, grp, cons, nt in (
-                ('jac_var', 'opty_jac_var', var_groups,
-                 [[] for _ in var_groups], False),
-                ('conjac_var', 'opty_conjac_var',
-                 list(var_fused) + [[(0, 0)]]*len(detached_sets),
-                 [[] for _ in var_fused] + detached_sets, nt_fused)):
-            src, meta = w.kernel(name, grp, cons, opts.waves, nt,
-                                 inst_lines=folded, order='block')
-            meta['order'] = 'dispatch'
-            parts += [src, '']
-            kernels[key] = meta
-            if opts.var_order == 'run':
-                # the run form of the same kernel, for a code object of its
-                # own (``meta['run']``): this module, and with it the full
-                # kernels' code, stays what it is without the form.  Printed
-                # by the same writer right behind the dispatch form: the
-                # node-invariant values it reads have their table slots
-                nslots = len(w.uni_slot)
-                src, meta = w.kernel(name, grp, cons, opts.waves, nt,
-                                     inst_lines=folded, order='block',
-                                     run=opts.var_persist)
-                assert len(w.uni_slot) == nslots
-                meta['order'] = 'run' if meta['run_persist'] else 'dispatch'
-                run_parts += [src, '']
-                run_kernels[key] = meta
-        w._restricted = False
+        parts += [kn.text, '']
+        kernels[key] = kn.meta
+        plans += kn.plans
+    restricted, (vparts, vkernels), (run_parts, run_kernels) = \
+        _restricted_section(prog, w, opts, groups, fused_jac, detached_sets,
+                            nt_fused, folded)
+    parts += vparts
+    kernels.update(vkernels)
     if prog.inst_con_out:
         src, meta = w.inst_kernel()
         parts += [src, '']
         kernels['inst'] = meta
     src, num_uniform, dynamic = w.uniform_kernel()
     parts += [src, '']
-    head = ['// generated by opty_amd.codegen.emit_hip -- do not edit',
-            '// %s' % opts.key(),
-            '#define OPTY_STORE_AUX %d' % opts.store_aux,
-            '#include "opty_device.h"', '']
-    if getattr(w, 'uses_park', False):
-        head += [_PARK_HELPERS, '']
-    if any(k.get('persist') for k in kernels.values()):
-        head += [_LOOP_HELPERS, '']
-    if opts.fast_trig == 2:
-        head += [_UNIFORM_TRIG_HELPERS, '']
-    source = '\n'.join(head + parts)
-    run = None
-    if run_kernels and all(k['run_persist'] for k in run_kernels.values()):
-        # (RUN_MARKER: how the library knows a code object of this form)
-        rhead = ['// generated by opty_amd.codegen.emit_hip (run form of the '
-                 'restricted kernels) -- do not edit', '// %s' % opts.key(),
-                 '#define OPTY_STORE_AUX %d' % opts.store_aux,
-                 '#include "opty_device.h"', '', _LOOP_HELPERS, '',
-                 'extern "C" __device__ __attribute__((used)) int %s = 1;'
-                 % RUN_MARKER, '']
-        if opts.fast_trig == 2:
-            rhead += [_UNIFORM_TRIG_HELPERS, '']
-        rsource = '\n'.join(rhead + run_parts)
-        run = dict(source=rsource, kernels=run_kernels,
-                   sha=hashlib.sha256(rsource.encode()).hexdigest())
+    trig = [_UNIFORM_TRIG_HELPERS] if opts.fast_trig == 2 else []
+    source = '\n'.join(_module_head(opts, '', [
+        block for block, user in ((_PARK_HELPERS, 'park_rows'),
+                                  (_LOOP_HELPERS, 'persist'))
+        if any(k.get(user) for k in kernels.values())] + trig) + parts)
     meta = dict(kernels=kernels,
                 groups=[[list(rg) for rg in grp] for grp in groups],
                 fused_groups=[[list(rg) for rg in grp] for grp in fused_jac],
@@ -2976,15 +2965,18 @@ def emit_module(prog, opts=None, node_blocks=None, literals=None):
                 inst_folded=bool(folded),
                 con_attached=bool(any(attached)),
                 sha=hashlib.sha256(source.encode()).hexdigest())
-    if run:
-        meta['run'] = run
-    if var_ranges:
-        meta['restricted'] = dict(
-            owner_ranges=[list(rg) for rg in var_ranges],
-            groups=[[list(rg) for rg in grp] for grp in var_groups],
-            fused_groups=[[list(rg) for rg in grp] for grp in var_fused])
-    if w._plans:
-        meta['plans'] = w._plans
+    if run_kernels and all(k['run_persist'] for k in run_kernels.values()):
+        # (RUN_MARKER: how the library knows a code object of this form)
+        rsource = '\n'.join(_module_head(
+            opts, ' (run form of the restricted kernels)', [
+                _LOOP_HELPERS, 'extern "C" __device__ __attribute__((used)) '
+                'int %s = 1;' % RUN_MARKER] + trig) + run_parts)
+        meta['run'] = dict(source=rsource, kernels=run_kernels,
+                           sha=hashlib.sha256(rsource.encode()).hexdigest())
+    if restricted:
+        meta['restricted'] = restricted
+    if plans:
+        meta['plans'] = plans
     if literals:
         meta['literals'] = len(literals)
     return source, meta

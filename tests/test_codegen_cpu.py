@@ -944,6 +944,61 @@ def test_automatic_work_aware_cut():
         assert m['geometry']['cut'] == 'even', name
 
 
+def test_printing_a_kernel_leaves_nothing_behind():
+    """A kernel in print lives in a record of its own (``emit_hip._Kernel``):
+    printing one twice from the same writer gives the same text and meta
+    both times, and nothing on the writer changes but the memo caches that
+    exist to be shared between kernels -- in the dispatch form, in the run
+    form and with waves that park values in LDS."""
+    import copy
+    from opty_amd.codegen import emit_hip as eh
+    memo = {'uni_slot', '_dyn', '_dense', '_wcost', '_auto', '_auto_work',
+            '_work_cut_objective', '_pub'}
+
+    def state(w):
+        return {k: v if k in ('p', 'dag') else copy.deepcopy(v)
+                for k, v in vars(w).items() if k not in memo}
+
+    def print_twice(w, *args, **kwargs):
+        before = state(w)
+        first = w.kernel(*args, **kwargs)
+        assert w.kernel(*args, **kwargs) == first
+        after = state(w)
+        assert vars(after.pop('o')) == vars(before.pop('o'))
+        assert after == before
+        for gone in ('_con_nt', '_pub_rows', '_park_rows', '_staged',
+                     '_restricted', 'uses_park', '_plans'):
+            assert not hasattr(w, gone), gone
+        return first
+
+    prog = ConstraintCollocator(
+        **problems.build('config3_10link_small'))._build_program()
+    opts = EmitOptions(var_order='run', restricted=1)
+    w = eh._ModuleWriter(prog, opts)
+    strips = w.restricted_strips(w.restricted_ranges(), 4)
+    args = ('opty_conjac_var', strips + [[(0, 0)]],
+            [[] for _ in strips] + [list(range(prog.M))], opts.waves)
+    text, meta = print_twice(w, *args, order='block', restricted=True)
+    assert not meta['run_persist'] and 'blk_prev' not in text
+    text, meta = print_twice(w, *args, order='block', restricted=True,
+                             run=opts.var_persist)
+    assert meta['run_persist'] == opts.var_persist and 'blk_prev' in text
+    # the muscle-driven leg with the options of its measured plan
+    prog = ConstraintCollocator(
+        **problems.build('one_legged_small'))._build_program()
+    opts = EmitOptions(chunk=16, groups=5, fused_groups=5, order='tail',
+                       fused_order='list', park=48, park_live=235,
+                       fused_strips='0:96;96:160;160:348', share_rcp=1)
+    w = eh._ModuleWriter(prog, opts)
+    groups = w.group_ranges()
+    print_twice(w, 'opty_jac', groups, [[] for _ in groups], opts.waves)
+    # ... and over the plan's three wide strips, whose waves do park
+    groups = w.explicit_strips(opts.fused_strips)
+    text, meta = print_twice(w, 'opty_jac', groups, [[] for _ in groups],
+                             opts.waves)
+    assert meta['park_rows'] > 0 and 'opty_unpark(' in text
+
+
 def test_spill_loop_falls_back_on_recomputation_per_chunk():
     """The muscle-driven leg under the midpoint rule: every cut of its block
     spills 24+ vector registers (with or without the constraint rows in the
