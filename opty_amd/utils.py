@@ -45,6 +45,18 @@ def coo_to_dense(values, rows, cols):
     return out
 
 
+def _matrix_program(dag, outputs, num_vec, num_const, shape):
+    """The matrix program of the row-major ``outputs`` (values of ``dag``)
+    as a ``shape`` matrix: what :class:`_MatrixFunction` prints, compiles
+    and loads."""
+    import os
+    from .codegen.program import matrix_program
+    if os.environ.get('OPTY_COLLECT', '1') != '0':
+        from .codegen.simplify import collect_coefficients
+        outputs = collect_coefficients(dag, list(outputs))
+    return matrix_program(dag, outputs, num_vec, num_const, shape)
+
+
 class _MatrixFunction(object):
     """``f(result, *num_args) -> result.reshape(n, rows, cols)``: the callable
     :func:`ufuncify_matrix` returns (``opty/utils.py:610-617``)."""
@@ -52,7 +64,6 @@ class _MatrixFunction(object):
     def __init__(self, dag, outputs, num_vec, const_positions, num_args,
                  shape, tmp_dir=None, show_compile_output=False, device=0,
                  emit_options=None):
-        from .codegen.program import matrix_program
         from .codegen.emit_hip import emit_matrix_module
         from . import hip_backend as hb
         self.shape = shape
@@ -62,12 +73,8 @@ class _MatrixFunction(object):
         self.vec_positions = tuple(k for k in range(num_args)
                                    if k not in self.const_positions)
         assert len(self.vec_positions) == num_vec
-        import os
-        if os.environ.get('OPTY_COLLECT', '1') != '0':
-            from .codegen.simplify import collect_coefficients
-            outputs = collect_coefficients(dag, list(outputs))
-        prog = matrix_program(dag, outputs, num_vec,
-                              len(self.const_positions), shape)
+        prog = _matrix_program(dag, outputs, num_vec,
+                               len(self.const_positions), shape)
         self.source, self.meta = emit_matrix_module(prog, emit_options)
         hsaco = hb.compile_module(self.source, tmp_dir, show_compile_output)
         k = self.meta['kernels']['jac']

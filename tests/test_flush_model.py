@@ -21,11 +21,13 @@ TS = 65
 def model_flush(calls, P, b0, nvalid, R):
     """calls: list of ('flush', NL, lo, own_lo, own_hi, avail) / ('head',)
     in program order for ONE wave, preceded by ('write', v) tile writes.
-    Returns dict position -> (node, entry) for everything stored, and the list
-    of (start, length) store extents."""
+    Returns dict position -> (node, entry) for everything stored, the list
+    of (start, length) store extents, and the positions among them that
+    ``opty_head_piece`` stored."""
     tile = {}
     stores = {}
     extents = []
+    head = []
     for call in calls:
         if call[0] == 'write':
             v = call[1]
@@ -40,6 +42,7 @@ def model_flush(calls, P, b0, nvalid, R):
                     assert lane not in stores
                     stores[lane] = (0, lane)
                     extents.append((lane, 1))
+                    head.append(lane)
         else:
             _, NL, lo, own_lo, own_hi, avail = call
             ppn = NL*8
@@ -77,7 +80,7 @@ def model_flush(calls, P, b0, nvalid, R):
                         pos = nd*P + vv
                         assert pos not in stores, pos
                         stores[pos] = (src[0], src[1])
-    return stores, extents
+    return stores, extents, head
 
 
 def parse_groups(source, kernel='opty_jac'):
@@ -125,13 +128,17 @@ def test_every_element_written_once(name, chunk, groups, interleave):
 
 
 def _check_exactly_once(source, groups, P, chunk, phases=(0, 1, 6, 15),
-                        counts=(64, 1, 37)):
+                        counts=(64, 1, 37), edges=None):
+    """``edges(P, b0, nvalid, heads, singles)``: called with the positions
+    ``opty_head_piece`` stored and those of the one-element stores of
+    ``opty_flush_lines`` (its straddling-piece branch)."""
     R = chunk + 16
     parsed = parse_groups(source)
     assert len(parsed) == len(groups)
     for b0 in phases:
         for nvalid in counts:
             stores = {}
+            heads, singles = [], []
             strips = [(rg, calls) for grp, pg in zip(groups, parsed)
                       for rg, calls in zip(grp, pg)]
             assert sum(len(g) for g in parsed) == len(strips)
@@ -149,7 +156,10 @@ def _check_exactly_once(source, groups, P, chunk, phases=(0, 1, 6, 15),
                     else:
                         seq.append(c)
                 assert v == e1 + 15
-                st, ext = model_flush(seq, P, b0, nvalid, R)
+                st, ext, head = model_flush(seq, P, b0, nvalid, R)
+                heads += head
+                singles += [pos for pos, ln in ext
+                            if ln == 1 and pos not in head]
                 for pos, src in st.items():
                     assert pos not in stores
                     stores[pos] = src
@@ -160,6 +170,8 @@ def _check_exactly_once(source, groups, P, chunk, phases=(0, 1, 6, 15),
             # 16-byte pieces from ONE flush call -> whole-line stores
             nlines = (b0 + nvalid*P)//16 - (b0 + 15)//16
             assert nlines > 0 or nvalid*P < 31
+            if edges is not None:
+                edges(P, b0, nvalid, sorted(heads), sorted(singles))
 
 
 def test_exactly_once_over_block_widths():
@@ -190,3 +202,49 @@ def test_exactly_once_over_block_widths():
                     phases=(0, 3, 8, 15), counts=(64, 1, 37))
                 runs += 1
     assert runs == 28*2*4
+
+
+def test_exactly_once_over_flush_cases():
+    """The model at what ``tests/test_flush_device_gpu.py`` runs on the GPU:
+    the first eight widths of the line mode (64..71, below the sweep above)
+    and every line-mode ``(P, options)`` of ``flush_cases.CASES``, printed as
+    the GPU tests' modules are; the phases and counts of the sweep above and
+    a block less one node.  Also holds ``flush_cases.straddles`` and
+    ``flush_cases.head_length`` -- from which
+    ``tests/test_flush_cases_cpu.py`` works out what the GPU sweep reaches --
+    to the model: the only one-element stores are the head piece's ``s``
+    and, where the block ends at an odd phase, its last element."""
+    import flush_cases as fc
+    from opty_amd.codegen import ir
+    from opty_amd.codegen.program import matrix_program
+    from opty_amd.codegen.emit_hip import emit_matrix_module, _ModuleWriter
+
+    def edges(P, b0, nvalid, heads, singles):
+        assert heads == list(range(fc.head_length(b0)))
+        assert singles == ([nvalid*P - 1] if fc.straddles(P, b0, nvalid)
+                           else [])
+
+    def ranges(prog, opts):
+        grp = _ModuleWriter(prog, opts).group_ranges()
+        return [[list(rg) for rg in g] for g in grp]
+    kwargs = dict(phases=(0, 3, 8, 15), counts=(64, 1, 37, 63), edges=edges)
+    runs = 0
+    for P in range(64, 72):
+        dag = ir.DAG()
+        x = dag.input('cur', 0)
+        prog = matrix_program(dag, [x]*P, 1, 0, (1, P))
+        for chunk in (16, 32, 64):
+            for groups in (None, 1, 2 + P % 3, 5):
+                opts = EmitOptions(chunk=chunk, groups=groups,
+                                   ablate='store_only')
+                source, _ = emit_matrix_module(prog, opts)
+                _check_exactly_once(source, ranges(prog, opts), P, chunk,
+                                    **kwargs)
+                runs += 1
+    assert runs == 8*3*4
+    for case in fc.LINE_CASES:
+        # the module the GPU test loads, and its program's strips
+        opts = fc.options(case.kw)
+        _check_exactly_once(fc.source(case.P, case.kw),
+                            ranges(fc.program(case.P), opts),
+                            case.P, opts.chunk, **kwargs)
