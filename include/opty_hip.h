@@ -174,7 +174,10 @@ typedef struct opty_hip_desc {
  * (8: the restricted kernels' geometry, opty_hip_output_*; 9: the
  * opty_hip_jacprod_* entry points; 10: the opty_hip_objhess_* entry points;
  * 11: the opty_hip_hessmv_* entry points; 12: opty_hip_hessmv_apply_block
- * and opty_hip_hessmv_block_width), and
+ * and opty_hip_hessmv_block_width; the opty_hip_jacprod_block_* entry points
+ * came later WITHOUT a new version: they are purely additive, no struct or
+ * signature of version 12 changed, and a client finds out whether its library
+ * has them by looking the symbols up), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -783,6 +786,55 @@ int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free,
                          const double *v, double *out, int32_t mem);
 int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free,
                          const double *w, double *out, int32_t mem);
+
+/* ---- block products: Y = J(free) V and G = J(free)^T W ----------------------
+ * The products above for `ncols` vectors in one call.  Column c of V is the
+ * num_free doubles at V + c*ldv, of Y the num_constraints doubles at Y +
+ * c*ldy; column c of W the num_constraints doubles at W + c*ldw, of G the
+ * num_free doubles at G + c*ldg.  A leading dimension may exceed the column
+ * length (interior blocks of a larger matrix): what lies between two result
+ * columns is never written, nothing outside the columns is read.
+ * The code object is a module of its own, generated for `width` (4 or 2)
+ * columns per pass: `opty_jvp_block` (grid.y = jvp_strips),
+ * `opty_jvp_block_inst`, `opty_vjp_block` (grid.y = vjp_strips) and
+ * `opty_vjp_block_fin`, the geometry of the four single kernels.  What does
+ * not depend on the column -- trig, the collected coefficients, the
+ * mass-matrix factors -- is evaluated once per pass; a call makes
+ * ceil(ncols/width) passes.  Every result element is written exactly once, in
+ * a fixed order of operations: the same inputs give the same bits (not
+ * necessarily those of the single products: the expressions are associated
+ * differently).
+ * Refused before anything is enqueued, each with the offending number: null
+ * pointers, ncols < 0, a leading dimension below the column length, a result
+ * range that overlaps `free` or the input block, a bad `mem`.  ncols == 0
+ * succeeds and launches nothing.  OPTY_HIP_HOST: synchronous, the columns are
+ * staged without their padding; OPTY_HIP_DEVICE: enqueued on the problem's
+ * stream.  The handle BORROWS its problem handle as opty_hip_jacprod does. */
+typedef struct opty_hip_jacprod_block opty_hip_jacprod_block;
+
+typedef struct opty_hip_jacprod_block_desc {
+    int32_t width;       /* K of the module: 2 or 4                            */
+    int32_t jvp_strips;  /* workgroups per 64-node block of opty_jvp_block     */
+    int32_t vjp_strips;  /* workgroups per 63-node block of opty_vjp_block     */
+    int32_t num_tail;    /* r + s: tail entries of `free` (block partials)     */
+    int32_t nnz_inst;    /* first partials of the instance constraints         */
+} opty_hip_jacprod_block_desc;
+
+int opty_hip_jacprod_block_create(opty_hip_problem *p,
+                                  const opty_hip_jacprod_block_desc *desc,
+                                  const char *code_object_path,
+                                  opty_hip_jacprod_block **out);
+int opty_hip_jacprod_block_destroy(opty_hip_jacprod_block *h);
+/* Columns per pass (the descriptor's width); -1 for a null handle. */
+int32_t opty_hip_jacprod_block_width(const opty_hip_jacprod_block *h);
+int opty_hip_jacprod_block_jvp(opty_hip_jacprod_block *h, const double *free,
+                               const double *V, int64_t ldv,
+                               double *Y, int64_t ldy,
+                               int32_t ncols, int32_t mem);
+int opty_hip_jacprod_block_vjp(opty_hip_jacprod_block *h, const double *free,
+                               const double *W, int64_t ldw,
+                               double *G, int64_t ldg,
+                               int32_t ncols, int32_t mem);
 
 /* ---- Hessian operator: y = H v from the stored triplets ----------------------
  * H is the symmetric matrix whose LOWER triangle is the SUM of the triplets of

@@ -56,28 +56,46 @@ def scalar_leaf(prog, vec='vec'):
         if dag.op[i] == ir.INPUT else None
 
 
+def node_input(prog, kind, k, vec='vec'):
+    """Source of input ``(kind, k)`` in a kernel whose lane evaluates
+    constraint node ``ic``; ``vec``: the kernel parameter that holds the
+    multipliers (``lam``) or the direction (``vcur`` / ``vadj`` / ``vpar`` /
+    ``vh``)."""
+    if kind in ('cur', 'adj', 'vcur', 'vadj'):
+        src, idx = prog.rows[k]
+        off = prog.cur_offset if kind.endswith('cur') else prog.adj_offset
+        if kind[0] == 'v':
+            assert src == 'free', (kind, k)
+            base = vec
+        else:
+            base = 'free_' if src == 'free' else 'known_traj'
+        return '%s[%dLL*N + ic + %d]' % (base, idx, off)
+    if kind == 'lam':
+        return '%s[%dLL*ncn + ic]' % (vec, k)
+    return scalar(prog, kind, k, vec)
+
+
 def node_leaf(prog, vec='vec'):
-    """``leaf(i)`` of a kernel whose lane evaluates constraint node ``ic``;
-    ``vec``: the kernel parameter that holds the multipliers (``lam``) or the
-    direction (``vcur`` / ``vadj`` / ``vpar`` / ``vh``)."""
+    """``leaf(i)`` of a kernel whose lane evaluates constraint node ``ic``
+    (:func:`node_input`)."""
+    dag = prog.dag
+    return lambda i: node_input(prog, *dag.args[i], vec=vec) \
+        if dag.op[i] == ir.INPUT else None
+
+
+def column_leaf(prog, source=node_input, vec='vec%d'):
+    """``leaf(i)`` of a block product kernel: ``source`` (:func:`node_input`
+    or :func:`scalar`) of the input within its column
+    (:func:`ir.split_column`), read from the column's own pointer ``vec %
+    column``."""
     dag = prog.dag
 
     def leaf(i):
         if dag.op[i] != ir.INPUT:
             return None
         kind, k = dag.args[i]
-        if kind in ('cur', 'adj', 'vcur', 'vadj'):
-            src, idx = prog.rows[k]
-            off = prog.cur_offset if kind.endswith('cur') else prog.adj_offset
-            if kind[0] == 'v':
-                assert src == 'free', (kind, k)
-                base = vec
-            else:
-                base = 'free_' if src == 'free' else 'known_traj'
-            return '%s[%dLL*N + ic + %d]' % (base, idx, off)
-        if kind == 'lam':
-            return '%s[%dLL*ncn + ic]' % (vec, k)
-        return scalar(prog, kind, k, vec)
+        c, k = ir.split_column(kind, k)
+        return source(prog, kind, k, vec % c)
     return leaf
 
 

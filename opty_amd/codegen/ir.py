@@ -49,10 +49,27 @@ UNARY = ('sqrt', 'sin', 'cos', 'tan', 'exp', 'log', 'abs', 'sign', 'asin',
 #: the same index sit in ``free`` (Jacobian-product programs,
 #: ``program.build_jacobian_product_program``); ``dir`` is the pseudo-column a
 #: tangent sweep differentiates along, never reachable from a root.
+#: Block product programs (``program.build_jacobian_block_product_program``)
+#: carry one copy of ``lam`` / ``vcur`` / ``vadj`` / ``vpar`` / ``vh`` / ``dir``
+#: per column of the block: column ``c``'s input has the index ``index +
+#: COLUMN_STRIDE*c`` (:func:`split_column`), so the kinds -- and with them
+#: ``UNIFORM_KINDS`` -- are those of the single program.
 INPUT_KINDS = ('cur', 'adj', 'par', 'h', 'free', 'lam', 'vcur', 'vadj',
                'vpar', 'vh', 'dir')
 #: kinds whose value is the same at every constraint node
 UNIFORM_KINDS = ('par', 'h', 'free', 'vpar', 'vh', 'dir')
+#: kinds that a block product program has once per column
+COLUMN_KINDS = ('lam', 'vcur', 'vadj', 'vpar', 'vh', 'dir')
+#: index distance between two columns' copies of an input of COLUMN_KINDS
+#: (above every equation, row and parameter count)
+COLUMN_STRIDE = 1 << 20
+
+
+def split_column(kind, index):
+    """``(column, index within the column)`` of an input: column 0 for the
+    kinds that do not depend on the column."""
+    return divmod(index, COLUMN_STRIDE) if kind in COLUMN_KINDS \
+        else (0, index)
 
 
 class DAG(object):

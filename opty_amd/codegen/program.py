@@ -421,6 +421,23 @@ def build_jacobian_product_program(discrete_eom, state_cur, state_adj,
     the tangent of ``r_i`` is ``dr_i v_x``, the adjoint goes through the
     same ``chain`` as :func:`build_program`'s.  The instance constraints
     contribute their first partials as in the Jacobian program."""
+    tan, adj, parts = _product_parts(
+        discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
+        num_known_traj, parameters, num_known_par, h_sym, variable_duration,
+        wrt, method, instance, implicit, 1)
+    return JacobianProductProgram(tan_out=tan[0], adj_out=adj[0], **parts)
+
+
+def _product_parts(discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
+                   num_known_traj, parameters, num_known_par, h_sym,
+                   variable_duration, wrt, method, instance, implicit,
+                   columns):
+    """What the single and the block product program share: ``(tan, adj,
+    parts)`` -- the tangent roots ``tan[c][j]`` and the adjoint roots
+    ``adj[c][k]`` of each of the ``columns`` columns, and the other keyword
+    arguments of the program.  Column ``c``'s inputs have the indices of
+    :func:`ir.split_column`; with one column the DAG is the single
+    program's, node for node."""
     dag, table, con_out = _front_end(discrete_eom, state_cur, state_adj,
                                      traj_cur, traj_adj, parameters, h_sym,
                                      method)
@@ -431,35 +448,43 @@ def build_jacobian_product_program(discrete_eom, state_cur, state_adj,
         # multiplication per collected term, not one per expanded term
         con_out = collect_coefficients(dag, con_out)
     wrt_nodes = [table[s] for s in wrt]
-    C = len(wrt)
+    C, M, K = len(wrt), len(con_out), int(columns)
+    stride = ir.COLUMN_STRIDE
 
     chain = {}
-    seed = dag.input('dir', 0)
+    seeds = [dag.input('dir', stride*c) for c in range(K)]
     tchain = {}
     for node in wrt_nodes:
         kind, idx = dag.args[node]
-        tchain[node] = [(seed, dag.input('v' + kind, idx))]
+        tchain[node] = [(seeds[c], dag.input('v' + kind, idx + stride*c))
+                        for c in range(K)]
     for k, st, kd in implicit:
         sides = ['cur'] + (['adj'] if method == 'midpoint' else [])
         for side in sides:
             link = dag.input(side, n + k)
             dr = dag.input(side, n + kd)
             chain[link] = [(dag.input(side, st), dr)]
-            tchain[link] = [(seed, dag.mul(dr, dag.input('v' + side, st)))]
-    tan = [row[0] for row in forward_jacobian(dag, con_out, [seed], tchain,
-                                              angle_pairs=True)]
-    lag = dag.sum([dag.mul(dag.input('lam', j), c)
-                   for j, c in enumerate(con_out)])
-    adj = forward_jacobian(dag, [lag], wrt_nodes, chain,
-                           angle_pairs=True)[0]
+            tchain[link] = [
+                (seeds[c], dag.mul(dr, dag.input('v' + side, st + stride*c)))
+                for c in range(K)]
+    rows = forward_jacobian(dag, con_out, seeds, tchain, angle_pairs=True)
+    flat_tan = [rows[j][c] for c in range(K) for j in range(M)]
+    lags = [dag.sum([dag.mul(dag.input('lam', j + stride*c), cj)
+                     for j, cj in enumerate(con_out)]) for c in range(K)]
+    flat_adj = [node for row in forward_jacobian(
+        dag, lags, wrt_nodes, chain, angle_pairs=True) for node in row]
     if collect:
         # ... and once more over each kernel's own roots (the two sets never
         # meet in one kernel); kept where it pays: re-collecting the
         # derivative of an already collected sum can also undo sharing
         def cost(roots):
             return sum(dag.count_ops(roots).values())
-        tan = min(tan, collect_coefficients(dag, list(tan)), key=cost)
-        adj = min(adj, collect_coefficients(dag, list(adj)), key=cost)
+        flat_tan = min(flat_tan, collect_coefficients(dag, list(flat_tan)),
+                       key=cost)
+        flat_adj = min(flat_adj, collect_coefficients(dag, list(flat_adj)),
+                       key=cost)
+    tan = [flat_tan[c*M:(c + 1)*M] for c in range(K)]
+    adj = [flat_adj[c*C:(c + 1)*C] for c in range(K)]
 
     inst_jac_out, inst_pairs, num_atoms, num_inst = [], [], 0, 0
     if instance is not None:
@@ -473,13 +498,47 @@ def build_jacobian_product_program(discrete_eom, state_cur, state_adj,
             inst_jac_out += forward_jacobian(dag, [node], nodes)[0]
             inst_pairs += [(k, pos[s]) for s in grads[k]]
 
-    return JacobianProductProgram(
-        dag=dag, tan_out=tan, adj_out=adj, con_out=con_out, jac_out=[],
+    return tan, adj, dict(
+        dag=dag, con_out=con_out, jac_out=[],
         adj_sides=[column_side(n, q, method, k) for k in range(C)],
-        M=len(con_out), C=C, inst_jac_out=inst_jac_out,
+        M=M, C=C, inst_jac_out=inst_jac_out,
         inst_pairs=inst_pairs, num_inst=num_inst, num_inst_atoms=num_atoms,
         **_layout(state_cur, traj_cur, num_known_traj, parameters,
                   num_known_par, variable_duration, method))
+
+
+class JacobianBlockProductProgram(JacobianProductProgram):
+    """Plain data of a block product program
+    (:func:`build_jacobian_block_product_program`): a
+    :class:`JacobianProductProgram` whose ``tan_out[c]`` / ``adj_out[c]`` are
+    the M tangent / C adjoint roots of column ``c`` of ``columns``, over the
+    column's own inputs (:func:`ir.split_column`).  ``adj_sides``,
+    ``row_columns()``, ``tail_columns()`` and the instance partials do not
+    depend on the column."""
+
+
+def build_jacobian_block_product_program(discrete_eom, state_cur, state_adj,
+                                         traj_cur, traj_adj, num_known_traj,
+                                         parameters, num_known_par, h_sym,
+                                         variable_duration, wrt, method,
+                                         instance=None, implicit=(),
+                                         columns=4):
+    """``J V`` and ``J^T W`` for ``columns`` columns at once: arguments and
+    construction as :func:`build_jacobian_product_program`'s, on ONE DAG --
+    one tangent sweep with a pseudo-column ``('dir', c)`` per column of ``V``
+    (seeds: the column's own ``vcur`` / ``vadj`` / ``vpar`` / ``vh``; the
+    implicit-trajectory rule ``dr v_x`` per column) and one adjoint sweep
+    over the ``columns`` Lagrangians ``sum_j lam_j^(c) c_j``.  What does not
+    depend on the direction -- trig, the collected coefficients, the
+    mass-matrix factors -- is one node for all columns."""
+    if int(columns) < 1:
+        raise ValueError('columns must be at least 1, got %r' % (columns,))
+    tan, adj, parts = _product_parts(
+        discrete_eom, state_cur, state_adj, traj_cur, traj_adj,
+        num_known_traj, parameters, num_known_par, h_sym, variable_duration,
+        wrt, method, instance, implicit, columns)
+    return JacobianBlockProductProgram(tan_out=tan, adj_out=adj,
+                                       columns=int(columns), **parts)
 
 
 def assemble_jvp(prog, N, tan, inst, v, atom_free_index):

@@ -870,6 +870,34 @@ class ConstraintCollocator(object):
             return base(kind, k)
         return inputs
 
+    def _build_jacprod_block_program(self, columns=4):
+        """The block product program of ``columns`` columns
+        (:func:`opty_amd.codegen.program.build_jacobian_block_product_program`),
+        built on first use, one per width."""
+        from .codegen.program import build_jacobian_block_product_program
+        cache = self.__dict__.setdefault('_jacprod_block_programs', {})
+        if columns not in cache:
+            logger.info('Lowering %d tangents and %d adjoints of the '
+                        'constraint function on one DAG.', columns, columns)
+            cache[columns] = build_jacobian_block_product_program(
+                *self._builder_arguments(), self._instance_placeholders(),
+                implicit=self._implicit_chain(), columns=columns)
+        return cache[columns]
+
+    def _jacprod_block_inputs(self, free, vecs, nodes, what):
+        """``inputs(kind, index)`` of a block product DAG at the constraint
+        nodes ``nodes``: :meth:`_jacprod_inputs` per column, ``vecs[:, c]``
+        the vector of the column the index names
+        (:func:`opty_amd.codegen.ir.split_column`)."""
+        from .codegen.ir import split_column
+        per_column = [self._jacprod_inputs(free, vecs[:, c], nodes, what)
+                      for c in range(vecs.shape[1])]
+
+        def inputs(kind, k):
+            c, k = split_column(kind, k)
+            return per_column[c](kind, k)
+        return inputs
+
     def _shared_inputs(self, prog, free, nodes):
         """``inputs(kind, index)`` for the kinds every program shares
         (``cur``, ``adj``, ``par``, ``h``, ``free``) at the nodes ``nodes``."""
@@ -961,6 +989,20 @@ class ConstraintCollocator(object):
         finally:
             for x in vecs + outs:
                 x.close()
+        return self._referee_products(
+            prog, prog.tan_out, prog.adj_out,
+            lambda nodes, what: self._jacprod_inputs(
+                free, v if what == 'jvp' else w, nodes, what), v, w, jv, jtw)
+
+    def _referee_products(self, prog, tan_out, adj_out, inputs, v, w, jv,
+                          jtw, subject=''):
+        """Holds ``jv = J v`` and ``jtw = J^T w`` to the roots ``tan_out`` /
+        ``adj_out`` of ``prog`` run as an instruction tape
+        (:meth:`_verify_jacprod`'s scheme); ``inputs(nodes, what)``: the
+        DAG's inputs at the constraint nodes ``nodes`` for ``what`` = ``'jvp'``
+        / ``'vjp'``."""
+        N = self.num_collocation_nodes
+        ncn, M = N - 1, prog.M
         atoms = self._atom_free_index()
         extra = [ncn - 2, ncn - 1]
         for f in atoms:
@@ -971,6 +1013,7 @@ class ConstraintCollocator(object):
         worst = [0.0]
 
         def check(what, have, want, bnd, mag):
+            what = subject + what
             worst[0] = max(worst[0], self._tape_check(what, have, want, bnd,
                                                       mag, what=what))
 
@@ -978,8 +1021,8 @@ class ConstraintCollocator(object):
             return self._tape_referee(prog, roots, inputs, count)
 
         # J v: the defect rows, then the instance rows
-        fin = self._jacprod_inputs(free, v, nodes, 'jvp')
-        val, bnd = referee(list(prog.tan_out), fin, len(nodes))
+        fin = inputs(nodes, 'jvp')
+        val, bnd = referee(list(tan_out), fin, len(nodes))
         for j in range(M):
             check('jvp equation %d' % j, jv[j*ncn + nodes], val[j], bnd[j],
                   np.abs(val[j]))
@@ -994,8 +1037,8 @@ class ConstraintCollocator(object):
                   (len(ts) + 1)*float(np.abs(terms).sum()))
 
         # J^T w: the trajectory rows on the window
-        rin = self._jacprod_inputs(free, w, nodes, 'vjp')
-        val, bnd = referee(list(prog.adj_out), rin, len(nodes))
+        rin = inputs(nodes, 'vjp')
+        val, bnd = referee(list(adj_out), rin, len(nodes))
         want, wb, mag = (np.zeros(self.num_free) for _ in range(3))
         seen = np.zeros(N + 1, dtype=bool)
         seen[nodes] = True
@@ -1027,13 +1070,11 @@ class ConstraintCollocator(object):
         # ... and the tail columns: sums over ALL constraint nodes
         tails = prog.tail_columns()
         if tails:
-            roots = [prog.adj_out[k] for _, k in tails]
+            roots = [adj_out[k] for _, k in tails]
             tot, tb, tm = (np.zeros(len(tails)) for _ in range(3))
             for a in range(0, ncn, self._JACPROD_TAIL_CHUNK):
                 part = np.arange(a, min(ncn, a + self._JACPROD_TAIL_CHUNK))
-                val, bnd = referee(
-                    roots, self._jacprod_inputs(free, w, part, 'vjp'),
-                    len(part))
+                val, bnd = referee(roots, inputs(part, 'vjp'), len(part))
                 tot += val.sum(axis=1)
                 tb += bnd.sum(axis=1)
                 tm += np.abs(val).sum(axis=1)
@@ -1057,6 +1098,206 @@ class ConstraintCollocator(object):
                 num_tail=prog.r + prog.s, nnz_inst=len(prog.inst_jac_out)),
                 hsaco), dict(meta, hsaco=hsaco)
         return self._ensure_derived('_jacprod', create, self._verify_jacprod)
+
+    _JACPROD_BLOCK_KERNELS = ('opty_jvp_block', 'opty_jvp_block_inst',
+                              'opty_vjp_block', 'opty_vjp_block_fin')
+    #: columns per pass of the block kernels, widest first
+    _JACPROD_BLOCK_WIDTHS = (4, 2)
+
+    def _build_jacprod_block_code_object(self):
+        """``(hsaco, meta)`` of the block product module: the widest of
+        ``_JACPROD_BLOCK_WIDTHS`` that has a build without vector spills --
+        each width through the ladder of :meth:`_build_jacprod_code_object`.
+        ``meta['width']`` is the module's width, ``meta['tried']`` the builds
+        of every width met; when every one spills ``hsaco`` is None and the
+        width 1: block calls then loop over the single kernels."""
+        from .codegen.emit_jacprod import emit_jacprod_block_module
+        tried = {}
+        for width in self._JACPROD_BLOCK_WIDTHS:
+            hsaco, cuts, meta = bl.spill_free_module(
+                emit_jacprod_block_module,
+                self._build_jacprod_block_program(width), self._compile,
+                self._JACPROD_BLOCK_KERNELS, self._JACPROD_STRIP_OPS)
+            if hsaco is None:
+                tried[width] = meta['tried']
+                continue
+            return hsaco, dict(meta, width=width, tried=tried,
+                               jvp_strips=max(1, len(cuts[0])),
+                               vjp_strips=max(1, len(cuts[1])))
+        logger.warning('every build of the block product kernels spills '
+                       'vector registers (%s): block products go column by '
+                       'column through the single kernels', tried)
+        return None, dict(width=1, tried=tried)
+
+    def _verify_jacprod_block(self, handle):
+        """Holds a block build to its expression DAG before first use:
+        :meth:`_verify_jacprod`'s scheme per column, on ``width`` distinct
+        random columns of ``V`` and ``W`` -- one pass with all columns active
+        and one with ``width - 1`` -- into device buffers that start as NaN
+        and whose leading dimension is larger than the column: what lies
+        between the columns, and the column past ``ncols``, must still be
+        NaN.  Raises :class:`hip_backend.BuildRejected`."""
+        K = handle.width
+        prog = self._build_jacprod_block_program(K)
+        nfree, ncon = self.num_free, self.num_constraints
+        rng = np.random.default_rng(29)
+        free = rng.uniform(-1.0, 1.0, nfree)
+        if self._variable_duration:
+            free[-1] = 0.01
+        V = rng.uniform(-1.0, 1.0, (nfree, K))
+        W = rng.uniform(-1.0, 1.0, (ncon, K))
+        self._sync_known(self._hip, free)
+        pad = 5
+        ldy, ldg = ncon + pad, nfree + pad
+        vecs = [hb.DeviceVector(x, self._device)
+                for x in (free, V.T, W.T)]
+        outs = [hb.DeviceVector(np.full(K*ld, np.nan), self._device)
+                for ld in (ldy, ldg, ldy, ldg)]
+        try:
+            handle.jvp_block(vecs[0], vecs[1], nfree, outs[0], ldy, K,
+                             hb.DEVICE)
+            handle.vjp_block(vecs[0], vecs[2], ncon, outs[1], ldg, K,
+                             hb.DEVICE)
+            handle.jvp_block(vecs[0], vecs[1], nfree, outs[2], ldy, K - 1,
+                             hb.DEVICE)
+            handle.vjp_block(vecs[0], vecs[2], ncon, outs[3], ldg, K - 1,
+                             hb.DEVICE)
+            self._hip.synchronize()
+            Y, G, Y1, G1 = (x.numpy().reshape(K, -1) for x in outs)
+        finally:
+            for x in vecs + outs:
+                x.close()
+        for name, full, part, n in (('jvp', Y, Y1, ncon), ('vjp', G, G1,
+                                                           nfree)):
+            if not (np.all(np.isnan(full[:, n:])) and
+                    np.all(np.isnan(part[:, n:]))):
+                raise hb.BuildRejected(
+                    'block %s wrote between two result columns' % name,
+                    dict(what=name))
+            if not np.all(np.isnan(part[K - 1])):
+                raise hb.BuildRejected(
+                    'block %s stored a column past ncols' % name,
+                    dict(what=name))
+            if not np.array_equal(part[:K - 1, :n].view(np.int64),
+                                  full[:K - 1, :n].view(np.int64)):
+                raise hb.BuildRejected(
+                    'block %s: a pass of %d columns and one of %d disagree'
+                    % (name, K, K - 1), dict(what=name))
+        worst, verdict = 0.0, {}
+        for c in range(K):
+            verdict = self._referee_products(
+                prog, prog.tan_out[c], prog.adj_out[c],
+                lambda nodes, what: self._jacprod_block_inputs(
+                    free, V if what == 'jvp' else W, nodes, what),
+                V[:, c], W[:, c], Y[c, :ncon], G[c, :nfree],
+                subject='column %d: ' % c)
+            worst = max(worst, verdict['worst_fraction_of_tolerance'])
+        return dict(verdict, columns=K, worst_fraction_of_tolerance=worst)
+
+    def _ensure_jacprod_block(self):
+        """The block product handle (built, checked and verified on first
+        use), or None when every block build spills: the block width is then
+        1 and block calls loop over the single kernels."""
+        if getattr(self, '_jacprod_block_width', None) == 1:
+            return None
+
+        class NoModule(Exception):
+            pass
+
+        def create(hip):
+            hsaco, meta = self._build_jacprod_block_code_object()
+            if hsaco is None:
+                raise NoModule(meta)
+            prog = self._build_jacprod_block_program(meta['width'])
+            return hb.HipJacobianBlockProduct(hip, dict(
+                width=meta['width'], jvp_strips=meta['jvp_strips'],
+                vjp_strips=meta['vjp_strips'], num_tail=prog.r + prog.s,
+                nnz_inst=len(prog.inst_jac_out)), hsaco), \
+                dict(meta, hsaco=hsaco)
+        try:
+            handle = self._ensure_derived('_jacprod_block', create,
+                                          self._verify_jacprod_block)
+        except NoModule as none:
+            self._ensure_jacprod()
+            self._jacprod_block_meta = dict(
+                none.args[0], hsaco=None,
+                verdict=self._jacprod_meta['verdict'])
+            self._jacprod_block_width = 1
+            return None
+        self._jacprod_block_width = handle.width
+        return handle
+
+    def _generate_block_product(self, which):
+        handle = self._ensure_jacprod_block()
+        single = self._generate_product(which)
+        hip = self._hip
+        nfree = self.num_free
+        name, nin, nout = ('V', nfree, self.num_constraints) \
+            if which == 'jvp' else ('W', self.num_constraints, nfree)
+        launch = None if handle is None else \
+            handle.jvp_block if which == 'jvp' else handle.vjp_block
+
+        def evaluate(free, X):
+            if hasattr(free, 'data_ptr'):
+                import torch
+                if tuple(free.shape) != (nfree,) or X.ndim != 2 or \
+                        X.shape[0] != nin:
+                    raise ValueError('free / %s have the wrong shape' % name)
+                free = free.to(torch.float64).contiguous()
+                # the columns of X are the rows of its transpose
+                cols = X.to(device=free.device,
+                            dtype=torch.float64).t().contiguous()
+                k = cols.shape[0]
+                if k == 1 or (launch is None and k):
+                    return torch.stack([single(free, col) for col in cols],
+                                       dim=1)
+                out = torch.empty((k, nout), dtype=torch.float64,
+                                  device=free.device)
+                if k:
+                    self._sync_known(hip, free.cpu().numpy()
+                                     if self._callable_known else None)
+                    torch.cuda.current_stream(free.device).synchronize()
+                    launch(free, cols, nin, out, nout, k, hb.DEVICE)
+                    hip.synchronize()
+                return out.t()
+            free = self._host_free(free)
+            if np.ndim(X) != 2 or np.shape(X)[0] != nin:
+                raise ValueError('{} must have shape ({}, k), got {}'.format(
+                    name, nin, np.shape(X)))
+            X = column_major(X)
+            k = X.shape[1]
+            out = np.empty((nout, k), dtype=np.float64, order='F')
+            if k == 1 or launch is None:
+                for c in range(k):
+                    out[:, c] = single(free, X[:, c])
+            elif k:
+                self._sync_known(hip, free)
+                launch(free, X, nin, out, nout, k, hb.HOST)
+            return out
+        evaluate.handle = handle
+        evaluate.width = 1 if handle is None else handle.width
+        return evaluate
+
+    def generate_jvp_block_function(self):
+        """Returns ``jmm(free, V) -> ndarray (num_constraints, k)``: ``J(free)
+        V`` for the ``k`` columns of ``V`` (shape ``(num_free, k)``) in one
+        call.  The block kernels take ``jmm.width`` columns per pass and
+        evaluate what does not depend on the column once per pass (DESIGN.md
+        section 10.1); with width 1 -- every block build spills -- and for ``k
+        == 1`` the columns go through :meth:`generate_jvp_function`, whose
+        bits they then have.  A NumPy ``V`` in either memory order is
+        converted once to column-major; the result is a new column-major
+        float64 array, bit-identical from call to call.
+
+        ``free`` and ``V`` may also be torch CUDA tensors; the result is then
+        a new CUDA tensor (nothing crosses PCIe)."""
+        return self._generate_block_product('jvp')
+
+    def generate_vjp_block_function(self):
+        """Returns ``jtmm(free, W) -> ndarray (num_free, k)``: ``J(free)^T W``
+        for the ``k`` columns of ``W`` (shape ``(num_constraints, k)``);
+        otherwise as :meth:`generate_jvp_block_function`."""
+        return self._generate_block_product('vjp')
 
     def _generate_product(self, which):
         handle = self._ensure_jacprod()
@@ -1130,13 +1371,20 @@ class ConstraintCollocator(object):
         ``scipy.sparse.linalg.LinearOperator`` of shape ``(num_constraints,
         num_free)``: ``matvec`` / ``rmatvec`` are :meth:`generate_jvp_function`
         / :meth:`generate_vjp_function` at that ``free`` (a copy is kept; a
-        torch CUDA tensor stays on the device).  Every product returns a new
+        torch CUDA tensor stays on the device), ``matmat`` / ``rmatmat`` one
+        block product each (:meth:`generate_jvp_block_function` /
+        :meth:`generate_vjp_block_function`).  Every product returns a new
         array."""
         from scipy.sparse.linalg import LinearOperator
         if getattr(self, '_jacprod_functions', None) is None:
             self._jacprod_functions = (self.generate_jvp_function(),
                                        self.generate_vjp_function())
         jvp, vjp = self._jacprod_functions
+        if getattr(self, '_jacprod_block_functions', None) is None:
+            self._jacprod_block_functions = (
+                self.generate_jvp_block_function(),
+                self.generate_vjp_block_function())
+        jmm, jtmm = self._jacprod_block_functions
         if hasattr(free, 'data_ptr'):
             import torch
             free = free.detach().clone()
@@ -1145,14 +1393,58 @@ class ConstraintCollocator(object):
                 x = torch.from_numpy(np.ascontiguousarray(
                     x, dtype=np.float64).reshape(-1)).to(free.device)
                 return f(free, x).cpu().numpy()
+
+            def apply_block(f, X):
+                if hasattr(X, 'data_ptr'):
+                    return f(free, X)
+                X = torch.from_numpy(column_major(X).T).to(free.device).t()
+                return f(free, X).cpu().numpy()
         else:
             free = self._host_free(free).copy()
 
             def apply(f, x):
                 return np.array(f(free, np.asarray(x).reshape(-1)))
-        return LinearOperator(
-            (self.num_constraints, self.num_free), dtype=np.float64,
-            matvec=lambda x: apply(jvp, x), rmatvec=lambda x: apply(vjp, x))
+
+            def apply_block(f, X):
+                if hasattr(X, 'data_ptr'):
+                    import torch
+                    return torch.from_numpy(np.ascontiguousarray(
+                        f(free, X.detach().cpu().numpy()))).to(X.device)
+                return f(free, X)
+
+        class JacobianOperator(LinearOperator):
+            """``matmat`` / ``rmatmat`` are one block product each
+            (:meth:`generate_jvp_block_function`); a CUDA block of vectors is
+            taken as it is (SciPy would convert it to an array) and answered
+            with a CUDA tensor."""
+
+            def __init__(op):
+                super().__init__(np.dtype(np.float64),
+                                 (self.num_constraints, self.num_free))
+
+            def _matvec(op, x):
+                return apply(jvp, x)
+
+            def _rmatvec(op, x):
+                return apply(vjp, x)
+
+            def _matmat(op, X):
+                return apply_block(jmm, X)
+
+            def _rmatmat(op, X):
+                return apply_block(jtmm, X)
+
+            def matmat(op, X):
+                if hasattr(X, 'data_ptr'):
+                    return apply_block(jmm, X)
+                return super().matmat(X)
+
+            def rmatmat(op, X):
+                if hasattr(X, 'data_ptr'):
+                    return apply_block(jtmm, X)
+                return super().rmatmat(X)
+
+        return JacobianOperator()
 
     # ------------------------------------------------------------------
     # Hessian operator: H v from the stored triplets (DESIGN.md section 11)

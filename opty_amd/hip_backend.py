@@ -421,6 +421,11 @@ class _JacprodDesc(ctypes.Structure):
         'jvp_strips', 'vjp_strips', 'num_tail', 'nnz_inst')]
 
 
+class _JacprodBlockDesc(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'width', 'jvp_strips', 'vjp_strips', 'num_tail', 'nnz_inst')]
+
+
 class _ObjDesc(ctypes.Structure):
     _fields_ = [('N', ctypes.c_int64), ('n', ctypes.c_int32),
                 ('q', ctypes.c_int32), ('r', ctypes.c_int32),
@@ -560,6 +565,19 @@ _SIGNATURES = {
     'opty_hip_jacprod_destroy': (ctypes.c_int, [_P]),
     'opty_hip_jacprod_jvp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_jacprod_vjp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    'opty_hip_jacprod_block_create': (ctypes.c_int,
+                                      [_P, ctypes.POINTER(_JacprodBlockDesc),
+                                       ctypes.c_char_p, ctypes.POINTER(_P)]),
+    'opty_hip_jacprod_block_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_jacprod_block_width': (ctypes.c_int32, [_P]),
+    'opty_hip_jacprod_block_jvp': (ctypes.c_int,
+                                   [_P, _P, _P, ctypes.c_int64, _P,
+                                    ctypes.c_int64, ctypes.c_int32,
+                                    ctypes.c_int32]),
+    'opty_hip_jacprod_block_vjp': (ctypes.c_int,
+                                   [_P, _P, _P, ctypes.c_int64, _P,
+                                    ctypes.c_int64, ctypes.c_int32,
+                                    ctypes.c_int32]),
     'opty_hip_hessmv_create': (ctypes.c_int,
                                [_P, ctypes.POINTER(_HessmvDesc),
                                 ctypes.POINTER(_P)]),
@@ -1392,6 +1410,38 @@ class HipJacobianProduct(_DerivedHandle):
     def vjp(self, free, w, out, mem):
         _check(self._lib.opty_hip_jacprod_vjp(self._handle(), _ptr(free),
                                               _ptr(w), _ptr(out), mem))
+
+
+class HipJacobianBlockProduct(_DerivedHandle):
+    """One ``opty_hip_jacprod_block`` handle: ``J(free) V`` and ``J(free)^T
+    W`` of a :class:`HipProblem` for several columns per pass, over a block
+    module of its own; borrows and follows the problem's C handle as
+    :class:`HipJacobianProduct` does."""
+
+    _create, _destroy = ('opty_hip_jacprod_block_create',
+                         'opty_hip_jacprod_block_destroy')
+
+    def __init__(self, problem, desc, hsaco_path):
+        self._desc = dict(desc)
+        super().__init__(problem, hsaco_path)
+
+    def _descriptor(self):
+        return _JacprodBlockDesc(**self._desc)
+
+    @property
+    def width(self):
+        """Columns per pass."""
+        return int(self._lib.opty_hip_jacprod_block_width(self._handle()))
+
+    def jvp_block(self, free, V, ldv, Y, ldy, ncols, mem):
+        _check(self._lib.opty_hip_jacprod_block_jvp(
+            self._handle(), _ptr(free), _ptr(V), ldv, _ptr(Y), ldy, ncols,
+            mem))
+
+    def vjp_block(self, free, W, ldw, G, ldg, ncols, mem):
+        _check(self._lib.opty_hip_jacprod_block_vjp(
+            self._handle(), _ptr(free), _ptr(W), ldw, _ptr(G), ldg, ncols,
+            mem))
 
 
 class HipHessianProduct(_DerivedHandle):
