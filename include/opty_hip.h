@@ -177,7 +177,9 @@ typedef struct opty_hip_desc {
  * and opty_hip_hessmv_block_width; the opty_hip_jacprod_block_* entry points
  * came later WITHOUT a new version: they are purely additive, no struct or
  * signature of version 12 changed, and a client finds out whether its library
- * has them by looking the symbols up), and
+ * has them by looking the symbols up; likewise, later still,
+ * opty_hip_jacprod_jvp_shard / opty_hip_jacprod_jvp_instance /
+ * opty_hip_jacprod_vjp_shard), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -786,6 +788,53 @@ int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free,
                          const double *v, double *out, int32_t mem);
 int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free,
                          const double *w, double *out, int32_t mem);
+
+/* ---- node-sharded products: a window of the constraint nodes ------------------
+ * What opty_hip_eval_shard is to the evaluation: the products of the rows
+ * (jvp) resp. onto the columns (vjp) that belong to the constraint nodes
+ * [node_begin, node_end) of the handle's GLOBAL problem, for a host that
+ * node-shards one problem over several GPUs.  Device pointers only, enqueued on
+ * the problem's stream.  `free`, `v` and `w` are the GLOBAL vectors at full
+ * length (num_free resp. num_constraints doubles); the kernels are the four
+ * above, launched over the window.
+ *   jvp_shard    : out[j*out_stride + (i - node_begin)] = (J v)[j*(N-1) + i],
+ *                  equation j, node i of the window.  out_stride = N-1 with
+ *                  out = global + node_begin writes in place, out_stride =
+ *                  node_end - node_begin gives a dense (M, count) block.
+ *   jvp_instance : the o instance rows (J v)[M*(N-1) + k] into out_tail; by
+ *                  whichever rank assembles the vector.
+ *   vjp_shard    : the window OWNS the time nodes p in [node_begin, node_end)
+ *                  and, when node_end == N-1, also p = N-1.
+ *                  out[R*out_stride + (p - node_begin)] = (J^T w)[R*N + p],
+ *                  free row R, owned p, the instance constraints' terms of
+ *                  the atoms at owned time nodes included.  out_stride = N
+ *                  with out = global + node_begin writes in place, out_stride
+ *                  = the number of owned nodes gives a dense block.
+ *                  tail_part[t], t < r + s: the window's share of the tail
+ *                  entry (J^T w)[(n+q)*N + t], the sum over the window's
+ *                  constraint nodes; the entry is the sum of the shares of
+ *                  the windows of a partition.  May be null when r + s == 0.
+ * Contract: every entry of jvp_shard, and every entry of vjp_shard's `out`,
+ * has the BITS of the whole-problem product (the same lane arithmetic, the
+ * same two-term sum, the same instance additions in the same order), for any
+ * partition; tail_part is deterministic per window, and for the window
+ * [0, N-1) bit-identical to the whole product's tail.  Nothing outside the
+ * window's slice of `out` is written.  An empty window succeeds, launches
+ * nothing and zero-fills tail_part.  Refused before anything is enqueued:
+ * null pointers, node_begin < 0, node_end > N-1, node_begin > node_end, an
+ * out_stride below the window's width. */
+int opty_hip_jacprod_jvp_shard(opty_hip_jacprod *h, const double *free,
+                               const double *v, double *out,
+                               int64_t out_stride, int64_t node_begin,
+                               int64_t node_end);
+int opty_hip_jacprod_jvp_instance(opty_hip_jacprod *h, const double *free,
+                                  const double *v,
+                                  double *out_tail /* o doubles */);
+int opty_hip_jacprod_vjp_shard(opty_hip_jacprod *h, const double *free,
+                               const double *w, double *out,
+                               int64_t out_stride,
+                               double *tail_part /* r + s doubles */,
+                               int64_t node_begin, int64_t node_end);
 
 /* ---- block products: Y = J(free) V and G = J(free)^T W ----------------------
  * The products above for `ncols` vectors in one call.  Column c of V is the

@@ -2,32 +2,47 @@
 (:func:`program.build_jacobian_product_program`): ``J(free) v`` and
 ``J(free)^T w`` without the matrix.
 
-``opty_jvp``: lane = constraint node, one 64-node block per ``blockIdx.x``;
-the M tangent roots are cut into strips (``blockIdx.y``).  Per-node inputs are
+The four kernels evaluate a WINDOW ``[wa, wb)`` of the constraint nodes of
+the global problem (a rank's share of a node-sharded problem; ``[0, N-1)`` is
+the whole problem): every load is from the GLOBAL ``free`` / ``v`` / ``w`` /
+known rows, the results go to ``out`` with row stride ``ostride`` and origin
+``wa`` (``ostride = N-1`` resp. ``N`` with ``out = global + wa`` writes in
+place, a smaller stride gives a dense block).  The window is wave-uniform: it
+costs scalar registers only, and a lane computes what it computes in the
+whole-problem launch.
+
+``opty_jvp``: lane = constraint node ``wa + 64 blockIdx.x + lane``; the M
+tangent roots are cut into strips (``blockIdx.y``).  Per-node inputs are
 coalesced loads of the ``free`` / known-trajectory rows and of the same rows
 of ``v``; the tail scalars of ``v`` are scalar loads.  Equation ``j`` of node
-``i`` is stored to ``out[j*(N-1) + i]``: one 512-byte segment per wave.
+``i`` is stored to ``out[j*ostride + (i - wa)]``: one 512-byte segment per
+wave.
 
-``opty_jvp_inst``: one lane, ``out[M*(N-1) + k] = sum_a dinst_k/datom_a
-v[idx_a]``.
+``opty_jvp_inst``: one lane, ``tail[k] = sum_a dinst_k/datom_a v[idx_a]``
+(``tail``: the ``o`` instance rows, ``out + M*(N-1)`` of the whole vector).
 
 ``opty_vjp``: lane = constraint node, the C adjoint roots.  The entry ``p`` of
 ``free`` row ``R`` is ``lo_R(i = p) + hi_R(i = p - 1)`` (``lo`` / ``hi``: the
 adjoint columns of the row with time offset 0 / 1), the missing term dropped
-at the two ends.  Consecutive blocks OVERLAP by one constraint node (block
-``b`` holds the nodes ``63 b .. 63 b + 63``): lane ``l >= 1`` writes entry
-``63 b + l`` from its own ``lo`` and lane ``l - 1``'s ``hi`` (handed over
-through LDS), lane 0 only hands over -- except in block 0, where it writes
-entry 0.  Every entry is written exactly once, by one lane, as one sum of two
-terms: no atomics, the same bits in every call.  The tail columns (unknown
-parameters, a free ``h``) are sums over all constraint nodes: a fixed
-butterfly over the wave (the duplicated lane 0 of a block ``b > 0`` counts as
-zero), one partial per block and column.
+at the two ends.  A window OWNS the time nodes ``p`` in ``[wa, wb)`` and, when
+``wb == N - 1``, also ``p = N - 1``; entry ``p`` goes to ``out[R*ostride + (p
+- wa)]``.  Consecutive blocks OVERLAP by one constraint node (block ``b``
+holds the nodes ``i0 + 63 b .. i0 + 63 b + 63``, ``i0 = wa`` for ``wa == 0``
+and the halo node ``wa - 1`` otherwise): lane ``l >= 1`` writes its entry from
+its own ``lo`` and lane ``l - 1``'s ``hi`` (handed over through LDS), lane 0
+only hands over -- except in block 0 of a window that starts at node 0, where
+it writes entry 0.  Every owned entry is written exactly once, by one lane, as
+one sum of two terms -- the same two terms whatever the window: no atomics,
+the same bits in every call and for every partition.  The tail columns
+(unknown parameters, a free ``h``) are sums over the window's constraint
+nodes: a fixed butterfly over the wave (lane 0 of a block that only hands over
+counts as zero), one partial per block and column.
 
 ``opty_vjp_fin``: one wave, after ``opty_vjp`` on the same stream: sums the
-block partials in a fixed order into the tail of the result, then lane 0 adds
-the instance constraints' ``w[M*(N-1) + k] dinst_k/datom_a`` to ``g[idx_a]``
-one after the other.
+window's block partials in a fixed order into the ``r + s`` doubles ``tail``
+(the tail of the result for the whole problem), then lane 0 adds the instance
+constraints' ``w[M*(N-1) + k] dinst_k/datom_a``, one after the other in pair
+order, to the entries of the atoms whose time node the window owns.
 
 Block products (:func:`emit_jacprod_block_module`, a module of its own):
 ``opty_jvp_block`` / ``opty_jvp_block_inst`` / ``opty_vjp_block`` /
@@ -41,14 +56,33 @@ from .emit_hip import _Body, _UNIFORM_TRIG_HELPERS
 from .emit_strips import (block_preamble, column_leaf, cut, kernel, node_leaf,
                           scalar, scalar_leaf, strip_switch)
 
-#: parameter list of the four kernels; mirrored by ``struct JacprodArgs`` in
-#: ``csrc/jacprod.cpp``.  ``vec``: ``v`` (jvp) or ``w`` (vjp); ``part``: the
-#: block partials of the tail columns, ``part[t*gridDim.x + block]``
-JACPROD_PARAMS = (
+
+def vjp_window_blocks(wa, wb, N):
+    """Blocks ``opty_vjp`` is launched with for the window ``[wa, wb)`` of an
+    ``N``-node problem (``opty_vjp_fin`` and ``csrc/jacprod.cpp`` compute the
+    same): the first block of a window that starts at node 0 writes 64
+    entries, every other block 63."""
+    pend = wb + (1 if wb == N - 1 else 0)
+    span = pend - wa - (1 if wa == 0 else 0)
+    return (span + VJP_STRIDE - 1)//VJP_STRIDE if span > 0 else 1
+
+#: what the single and the block kernels share.  ``vec``: ``v`` (jvp) or ``w``
+#: (vjp); ``part``: the block partials of the tail columns,
+#: ``part[t*gridDim.x + block]``
+_SHARED_PARAMS = (
     'const double *__restrict__ free_, const double *__restrict__ known_traj, '
     'const double *__restrict__ params, const double *__restrict__ vec, '
     'const long long *__restrict__ inst_idx, double *__restrict__ out, '
     'double *__restrict__ part, double h, long long N')
+
+#: parameter list of the four kernels; mirrored by ``struct JacprodArgs`` in
+#: ``csrc/jacprod.cpp``.  ``[wa, wb)``: the window of constraint nodes;
+#: ``ostride``: row stride of ``out``, whose first column is node ``wa``;
+#: ``tail``: the ``o`` instance rows (``opty_jvp_inst``) or the ``r + s`` tail
+#: sums (``opty_vjp_fin``)
+JACPROD_PARAMS = _SHARED_PARAMS + (
+    ', long long wa, long long wb, long long ostride, '
+    'double *__restrict__ tail')
 
 #: constraint nodes a block of ``opty_vjp`` advances by (64 lanes, one shared)
 VJP_STRIDE = 63
@@ -90,8 +124,9 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
     jcut = cut(dag, [[node] for node in prog.tan_out], budget)
     lines = ['const int lane = threadIdx.x;',
              'const long long ncn = N - 1;',
-             'const long long i = (long long)blockIdx.x*64 + lane;',
-             'if ((long long)blockIdx.x*64 >= ncn) return;',
+             'const long long i0 = wa + (long long)blockIdx.x*64;',
+             'if (i0 >= wb) return;',
+             'const long long i = i0 + lane;',
              'const long long ic = i < ncn ? i : ncn - 1;']
     bodies = []
     for j0, j1 in jcut:
@@ -104,8 +139,8 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
             else:
                 body.begin_entry()
             ref = body.emit(prog.tan_out[j])
-            body.lines.append('if (i < ncn) out[%dLL*ncn + i] = %s;'
-                              % (j, ref))
+            body.lines.append('if (i < wb) out[%dLL*ostride + (i - wa)] = '
+                              '%s;' % (j, ref))
         body.end_scope()
         bodies.append(body.lines)
     strip_switch(lines, bodies)
@@ -114,8 +149,7 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
     # ---- opty_jvp_inst --------------------------------------------------
     body = _Body(dag, set(dag.reachable(prog.inst_jac_out)),
                  scalar_leaf(prog), fast_trig)
-    lines = ['if (threadIdx.x != 0 || blockIdx.x != 0) return;',
-             'const long long ncn = N - 1;']
+    lines = ['if (threadIdx.x != 0 || blockIdx.x != 0) return;']
     for k in range(prog.num_inst):
         terms = [(t, a) for t, (kk, a) in enumerate(prog.inst_pairs)
                  if kk == k]
@@ -123,7 +157,7 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
         for t, a in terms:
             ref = body.emit(prog.inst_jac_out[t])
             body.lines.append('acc%d += %s*vec[inst_idx[%d]];' % (k, ref, a))
-        body.lines.append('out[%dLL*ncn + %d] = acc%d;' % (M, k, k))
+        body.lines.append('tail[%d] = acc%d;' % (k, k))
         body.end_scope()
     src += kernel('opty_jvp_inst', JACPROD_PARAMS, lines + body.lines)
 
@@ -135,14 +169,29 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
             return [prog.adj_out[k] for k in unit[2:] if k is not None]
         return [prog.adj_out[unit[2]]]
     vcut = cut(dag, [roots_of(u) for u in units], budget)
-    lines = ['__shared__ double ex[2*64];'] + block_preamble(VJP_STRIDE) + [
-             '// this lane evaluates a constraint node of its own',
-             'const bool valid = i < ncn;',
-             '// ... that no other block counts (lane 0 repeats the last '
-             'lane of the previous block)',
-             'const bool counted = valid && (lane > 0 || blockIdx.x == 0);',
+    lines = ['__shared__ double ex[2*64];',
+             'const int lane = threadIdx.x;',
+             'const long long ncn = N - 1;',
+             '// a window that does not start the trajectory evaluates the '
+             'node before it for its upper terms',
+             'const long long i0 = wa - (wa > 0 ? 1 : 0) + '
+             '(long long)blockIdx.x*%d;' % VJP_STRIDE,
+             'if (i0 >= wb) return;',
+             'const long long i = i0 + lane;',
+             'const long long ic = i < ncn ? i : ncn - 1;',
+             '// the owned time nodes end here: the last window also owns '
+             'node N - 1',
+             'const long long pend = wb + (wb == ncn ? 1 : 0);',
+             '// lane 0 has an entry of its own only where the trajectory '
+             'starts',
+             'const bool first = lane > 0 || (blockIdx.x == 0 && wa == 0);',
+             '// this lane evaluates a constraint node of the window',
+             'const bool valid = i < wb;',
+             '// ... that no other block counts and that is no halo (lane 0 '
+             'repeats the last lane of the previous block)',
+             'const bool counted = valid && first;',
              '// entry i of a row is this lane\'s to write',
-             'const bool writer = i < N && (lane > 0 || blockIdx.x == 0);']
+             'const bool writer = i < pend && first;']
     bodies = []
     for u0, u1 in vcut:
         needed = set()
@@ -158,7 +207,7 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
                 body.begin_entry()
             if u[0] == 'row':
                 _, R, lo, hi = u
-                dst = 'out[%dLL*N + i]' % R
+                dst = 'out[%dLL*ostride + (i - wa)]' % R
                 hi_ref = body.emit(prog.adj_out[hi]) if hi is not None \
                     else None
                 if hi_ref is not None and forget:
@@ -205,27 +254,35 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
 
     # ---- opty_vjp_fin -------------------------------------------------------
     T = len(prog.tail_columns())
-    tail0 = '%dLL*N' % (prog.n + prog.q)
     lines = ['if (blockIdx.x != 0) return;',
              'const int lane = threadIdx.x;',
              'const long long ncn = N - 1;',
-             'const long long nblk = (ncn + %d)/%d;'
+             'const long long pend = wb + (wb == ncn ? 1 : 0);',
+             '// the blocks opty_vjp was launched with (vjp_window_blocks)',
+             'const long long span = pend - wa - (wa == 0 ? 1 : 0);',
+             'const long long nblk = span > 0 ? (span + %d)/%d : 1;'
              % (VJP_STRIDE - 1, VJP_STRIDE),
-             '(void)ncn; (void)nblk;']
+             '(void)ncn; (void)pend; (void)nblk;']
     for t, (j, _) in enumerate(prog.tail_columns()):
         lines += ['{',
                   '    double acc = 0.0;',
                   '    for (long long b = lane; b < nblk; b += 64) '
                   'acc += part[%dLL*nblk + b];' % t,
                   '    acc = opty_wave_sum(acc);',
-                  '    if (lane == 0) out[%s + %d] = acc;' % (tail0, j),
+                  '    if (lane == 0) tail[%d] = acc;' % j,
                   '}']
     body = _Body(dag, set(dag.reachable(prog.inst_jac_out)),
                  scalar_leaf(prog), fast_trig)
     for t, (k, a) in enumerate(prog.inst_pairs):
         ref = body.emit(prog.inst_jac_out[t])
-        body.lines.append('out[inst_idx[%d]] += vec[%dLL*ncn + %d]*%s;'
-                          % (a, M, k, ref))
+        # the atom is entry p of row R; the window that owns p adds
+        body.lines += [
+            '{',
+            '    const long long R = inst_idx[%d]/N, p = inst_idx[%d] - R*N;'
+            % (a, a),
+            '    if (p >= wa && p < pend) out[R*ostride + (p - wa)] += '
+            'vec[%dLL*ncn + %d]*%s;' % (M, k, ref),
+            '}']
     body.end_scope()
     if body.lines:
         lines += ['if (lane == 0) {'] + ['    ' + ln for ln in body.lines] + \
@@ -240,7 +297,7 @@ def emit_jacprod_module(prog, budget=1500, forget=False, fast_trig=1):
 #: argument starts at ``vec + c*ldv``, of the result at ``out + c*ldo``;
 #: ``ncols``: the active columns of the pass, ``1 <= ncols <= K``; ``part``:
 #: ``part[(t*K + c)*gridDim.x + block]``
-JACPROD_BLOCK_PARAMS = JACPROD_PARAMS + ', long long ldv, long long ldo, ' \
+JACPROD_BLOCK_PARAMS = _SHARED_PARAMS + ', long long ldv, long long ldo, ' \
     'int ncols'
 
 

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <vector>
 
 using namespace opty;
 
@@ -36,8 +37,12 @@ struct JacprodArgs {
     double *part;
     double h;
     long long N;
+    long long wa, wb;      // the window of constraint nodes
+    long long ostride;     // row stride of `out`; its first column is node wa
+    double *tail;          // opty_jvp_inst: the o instance rows;
+                           // opty_vjp_fin: the r + s tail sums
 };
-static_assert(sizeof(JacprodArgs) == 72,
+static_assert(sizeof(JacprodArgs) == 104,
               "JacprodArgs must match JACPROD_PARAMS");
 
 // ... and of the four block kernels (JACPROD_BLOCK_PARAMS)
@@ -68,12 +73,20 @@ struct opty_hip_jacprod : Borrowed {
     hipFunction_t k_jvp = nullptr, k_jvp_inst = nullptr, k_vjp = nullptr,
                   k_vjp_fin = nullptr;
     double *d_part = nullptr;   // num_tail partials per block of opty_vjp
+    std::vector<double> zero_tail;  // what an empty window's tail sums are
     // staging for host callers
     double *d_free = nullptr, *d_vec = nullptr, *d_out = nullptr;
     long long ncn() const { return p->d.N - 1; }
-    long long vjp_blocks() const {
-        return (ncn() + kVjpStride - 1)/kVjpStride;
+    // blocks of opty_vjp for the window [wa, wb) (vjp_window_blocks of
+    // emit_jacprod.py; opty_vjp_fin computes the same): the first block of a
+    // window that starts at node 0 writes 64 entries, every other block 63
+    long long vjp_blocks(long long wa, long long wb) const {
+        const long long pend = wb + (wb == ncn() ? 1 : 0);
+        const long long span = pend - wa - (wa == 0 ? 1 : 0);
+        return span > 0 ? (span + kVjpStride - 1)/kVjpStride : 1;
     }
+    // ... for the largest window, the whole problem
+    long long vjp_blocks() const { return vjp_blocks(0, ncn()); }
 };
 
 struct opty_hip_jacprod_block : Borrowed {
@@ -187,9 +200,10 @@ int run_block(opty_hip_jacprod_block *h, const double *free_,
     return 0;
 }
 
-// One product: `nvec` doubles of `vec` in, `nout` doubles out.
+// One product of the whole problem (`jvp`, or vjp): `nvec` doubles of `vec`
+// in, `nout` doubles out.
 template <typename Launch>
-int run(opty_hip_jacprod *h, const double *free_, const double *vec,
+int run(opty_hip_jacprod *h, bool jvp, const double *free_, const double *vec,
         size_t nvec, double *out, size_t nout, int32_t mem, Launch launch) {
     if (!h || !free_ || !vec || !out) return fail("null argument");
     if (int rc = borrowed_begin(h, mem, true)) return rc;
@@ -209,6 +223,13 @@ int run(opty_hip_jacprod *h, const double *free_, const double *vec,
         a.out = h->d_out;
     }
     borrowed_args(&a, p, free_);
+    // the whole problem: every constraint node, the vector's own strides,
+    // the instance rows / tail sums where the vector has them
+    a.wa = 0;
+    a.wb = h->ncn();
+    a.ostride = jvp ? h->ncn() : (long long)p->d.N;
+    a.tail = a.out + (jvp ? (size_t)p->d.M*(size_t)h->ncn()
+                          : nfree - (size_t)h->d.num_tail);
     size_t size = sizeof a;
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
                       HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
@@ -220,6 +241,37 @@ int run(opty_hip_jacprod *h, const double *free_, const double *vec,
         return host_done(h);
     }
     return 0;
+}
+
+// The window check the *_shard entry points share.
+int check_window(const opty_hip_jacprod *h, int64_t a, int64_t b) {
+    if (a < 0 || b > (int64_t)h->ncn() || a > b)
+        return fail("node window [%lld, %lld) is not within the %lld "
+                    "constraint nodes", (long long)a, (long long)b,
+                    h->ncn());
+    return 0;
+}
+
+// One windowed launch sequence on the problem's stream, device pointers only.
+template <typename Launch>
+int run_window(opty_hip_jacprod *h, const double *free_, const double *vec,
+               double *out, int64_t out_stride, double *tail, int64_t wa,
+               int64_t wb, Launch launch) {
+    if (int rc = borrowed_begin(h, OPTY_HIP_DEVICE, true)) return rc;
+    JacprodArgs a{};
+    borrowed_args(&a, h->p, free_);
+    a.vec = vec;
+    a.out = out;
+    a.part = h->d_part;
+    a.wa = wa;
+    a.wb = wb;
+    a.ostride = out_stride;
+    a.tail = tail;
+    size_t size = sizeof a;
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
+                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                      HIP_LAUNCH_PARAM_END};
+    return launch(config);
 }
 
 }  // namespace
@@ -285,8 +337,8 @@ int opty_hip_jacprod_jvp(opty_hip_jacprod *h, const double *free_,
     if (!h) return fail("null argument");
     opty_hip_problem *p = h->p;
     const long long nblk = (h->ncn() + 63)/64;
-    return run(h, free_, v, (size_t)p->num_free(), out, (size_t)p->num_con(),
-               mem, [&](void **config) -> int {
+    return run(h, true, free_, v, (size_t)p->num_free(), out,
+               (size_t)p->num_con(), mem, [&](void **config) -> int {
         if (p->d.M > 0)
             HIP_TRY(hipModuleLaunchKernel(h->k_jvp, (unsigned)nblk,
                                           (unsigned)h->d.jvp_strips, 1, 64, 1,
@@ -302,11 +354,84 @@ int opty_hip_jacprod_vjp(opty_hip_jacprod *h, const double *free_,
                          const double *w, double *out, int32_t mem) {
     if (!h) return fail("null argument");
     opty_hip_problem *p = h->p;
-    return run(h, free_, w, (size_t)p->num_con(), out, (size_t)p->num_free(),
-               mem, [&](void **config) -> int {
+    return run(h, false, free_, w, (size_t)p->num_con(), out,
+               (size_t)p->num_free(), mem, [&](void **config) -> int {
         HIP_TRY(hipModuleLaunchKernel(h->k_vjp, (unsigned)h->vjp_blocks(),
                                       (unsigned)h->d.vjp_strips, 1, 64, 1, 1,
                                       0, h->stream, nullptr, config));
+        if (h->d.num_tail > 0 || h->d.nnz_inst > 0)
+            HIP_TRY(hipModuleLaunchKernel(h->k_vjp_fin, 1, 1, 1, 64, 1, 1, 0,
+                                          h->stream, nullptr, config));
+        return 0;
+    });
+}
+
+int opty_hip_jacprod_jvp_shard(opty_hip_jacprod *h, const double *free_,
+                               const double *v, double *out,
+                               int64_t out_stride, int64_t node_begin,
+                               int64_t node_end) {
+    if (!h || !free_ || !v || !out) return fail("null argument");
+    if (int rc = check_window(h, node_begin, node_end)) return rc;
+    if (out_stride < node_end - node_begin)
+        return fail("out_stride %lld < the %lld nodes of the window",
+                    (long long)out_stride,
+                    (long long)(node_end - node_begin));
+    if (node_begin == node_end || h->p->d.M == 0) return 0;
+    const long long nblk = (node_end - node_begin + 63)/64;
+    return run_window(h, free_, v, out, out_stride, nullptr, node_begin,
+                      node_end, [&](void **config) -> int {
+        HIP_TRY(hipModuleLaunchKernel(h->k_jvp, (unsigned)nblk,
+                                      (unsigned)h->d.jvp_strips, 1, 64, 1, 1,
+                                      0, h->stream, nullptr, config));
+        return 0;
+    });
+}
+
+int opty_hip_jacprod_jvp_instance(opty_hip_jacprod *h, const double *free_,
+                                  const double *v, double *out_tail) {
+    if (!h || !free_ || !v) return fail("null argument");
+    if (h->p->d.num_inst == 0) return 0;
+    if (!out_tail) return fail("null argument");
+    return run_window(h, free_, v, nullptr, 0, out_tail, 0, 0,
+                      [&](void **config) -> int {
+        HIP_TRY(hipModuleLaunchKernel(h->k_jvp_inst, 1, 1, 1, 64, 1, 1, 0,
+                                      h->stream, nullptr, config));
+        return 0;
+    });
+}
+
+int opty_hip_jacprod_vjp_shard(opty_hip_jacprod *h, const double *free_,
+                               const double *w, double *out,
+                               int64_t out_stride, double *tail_part,
+                               int64_t node_begin, int64_t node_end) {
+    if (!h || !free_ || !w || !out) return fail("null argument");
+    if (h->d.num_tail > 0 && !tail_part)
+        return fail("null tail_part, but the problem has %d tail entries",
+                    h->d.num_tail);
+    if (int rc = check_window(h, node_begin, node_end)) return rc;
+    // the time nodes the window owns: the last window also owns node N - 1
+    const int64_t owned = node_end - node_begin +
+        (node_end > node_begin && node_end == (int64_t)h->ncn() ? 1 : 0);
+    if (out_stride < owned)
+        return fail("out_stride %lld < the %lld time nodes the window owns",
+                    (long long)out_stride, (long long)owned);
+    if (node_begin == node_end) {
+        // nothing to evaluate: the window's share of the tail sums is zero
+        if (int rc = borrowed_begin(h, OPTY_HIP_DEVICE, true)) return rc;
+        if (h->d.num_tail > 0) {
+            h->zero_tail.assign((size_t)h->d.num_tail, 0.0);
+            HIP_TRY(hipMemcpyAsync(tail_part, h->zero_tail.data(),
+                                   (size_t)h->d.num_tail*sizeof(double),
+                                   hipMemcpyHostToDevice, h->stream));
+        }
+        return 0;
+    }
+    return run_window(h, free_, w, out, out_stride, tail_part, node_begin,
+                      node_end, [&](void **config) -> int {
+        HIP_TRY(hipModuleLaunchKernel(
+            h->k_vjp, (unsigned)h->vjp_blocks(node_begin, node_end),
+            (unsigned)h->d.vjp_strips, 1, 64, 1, 1, 0, h->stream, nullptr,
+            config));
         if (h->d.num_tail > 0 || h->d.nnz_inst > 0)
             HIP_TRY(hipModuleLaunchKernel(h->k_vjp_fin, 1, 1, 1, 64, 1, 1, 0,
                                           h->stream, nullptr, config));

@@ -3738,6 +3738,11 @@ class ShardedProblem(Problem):
     the ROOT's known maps between solves are all supported; the CSR layout is
     not sharded.
 
+    :meth:`jacobian_operator` gives the matrix-free products ``J v`` / ``J^T
+    w`` of the sharded problem; block products, the Hessian
+    (``obj_hessian``, :meth:`hessian_operator`) and ``ufuncify_matrix`` are
+    not sharded.
+
     Extra keywords: ``group`` (process group), ``root`` (solver rank),
     ``torch_device`` (default ``cuda:<device>``).
     """
@@ -3781,7 +3786,46 @@ class ShardedProblem(Problem):
                 cols)
 
     def jacobian_operator(self, free):
-        raise NotImplementedError('Jacobian products are not sharded.')
+        """Root: the constraint Jacobian at ``free`` as the
+        ``scipy.sparse.linalg.LinearOperator`` of
+        :meth:`Problem.jacobian_operator` -- shape ``(num_constraints,
+        num_free)``, float64 -- whose ``matvec`` / ``rmatvec`` are evaluated
+        by all ranks, each on its window of the constraint nodes
+        (:meth:`opty_amd.sharded.ShardedCallbacks.jvp` / ``vjp``; the serving
+        ranks answer from :meth:`serve`).  Every entry but the node-invariant
+        tail of ``J^T w`` has the bits of the single-GPU operator's; the tail
+        is the sum of the ranks' shares in rank order.  ``matmat`` /
+        ``rmatmat`` loop over the columns: block products, like the Hessian
+        and ``ufuncify_matrix``, are not sharded."""
+        from scipy.sparse.linalg import LinearOperator
+        cb = self.callbacks
+        free = np.array(free, dtype=np.float64).reshape(-1)
+        shape = (self.sharded.num_constraints, self.sharded._num_free())
+
+        def columns(f, X, rows):
+            X = np.asarray(X, dtype=np.float64)
+            out = np.empty((rows, X.shape[1]))
+            for c in range(X.shape[1]):
+                out[:, c] = f(free, X[:, c])
+            return out
+
+        class ShardedJacobianOperator(LinearOperator):
+            def __init__(op):
+                super().__init__(np.dtype(np.float64), shape)
+
+            def _matvec(op, x):
+                return cb.jvp(free, np.asarray(x).reshape(-1))
+
+            def _rmatvec(op, x):
+                return cb.vjp(free, np.asarray(x).reshape(-1))
+
+            def _matmat(op, X):
+                return columns(cb.jvp, X, shape[0])
+
+            def _rmatmat(op, X):
+                return columns(cb.vjp, X, shape[1])
+
+        return ShardedJacobianOperator()
 
     def serve(self):
         """Non-root ranks: evaluate on the root's command until shutdown."""

@@ -565,6 +565,11 @@ _SIGNATURES = {
     'opty_hip_jacprod_destroy': (ctypes.c_int, [_P]),
     'opty_hip_jacprod_jvp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_jacprod_vjp': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
+    'opty_hip_jacprod_jvp_shard': (ctypes.c_int, [
+        _P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'opty_hip_jacprod_jvp_instance': (ctypes.c_int, [_P, _P, _P, _P]),
+    'opty_hip_jacprod_vjp_shard': (ctypes.c_int, [
+        _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64]),
     'opty_hip_jacprod_block_create': (ctypes.c_int,
                                       [_P, ctypes.POINTER(_JacprodBlockDesc),
                                        ctypes.c_char_p, ctypes.POINTER(_P)]),
@@ -1410,6 +1415,29 @@ class HipJacobianProduct(_DerivedHandle):
     def vjp(self, free, w, out, mem):
         _check(self._lib.opty_hip_jacprod_vjp(self._handle(), _ptr(free),
                                               _ptr(w), _ptr(out), mem))
+
+    def jvp_shard(self, free, v, out, out_stride, node_begin, node_end):
+        """``J v`` of the constraint nodes ``[node_begin, node_end)`` from the
+        global device ``free`` / ``v``; see ``opty_hip_jacprod_jvp_shard``
+        in ``include/opty_hip.h``."""
+        _check(self._lib.opty_hip_jacprod_jvp_shard(
+            self._handle(), _ptr(free), _ptr(v), _ptr(out), int(out_stride),
+            int(node_begin), int(node_end)))
+
+    def jvp_instance(self, free, v, out_tail):
+        """The ``o`` instance rows of ``J v`` into the device buffer
+        ``out_tail`` (``opty_hip_jacprod_jvp_instance``)."""
+        _check(self._lib.opty_hip_jacprod_jvp_instance(
+            self._handle(), _ptr(free), _ptr(v), _ptr(out_tail)))
+
+    def vjp_shard(self, free, w, out, out_stride, tail_part, node_begin,
+                  node_end):
+        """``J^T w`` on the time nodes the window ``[node_begin, node_end)``
+        owns and the window's share ``tail_part`` of the tail entries; see
+        ``opty_hip_jacprod_vjp_shard``."""
+        _check(self._lib.opty_hip_jacprod_vjp_shard(
+            self._handle(), _ptr(free), _ptr(w), _ptr(out), int(out_stride),
+            _ptr(tail_part), int(node_begin), int(node_end)))
 
 
 class HipJacobianBlockProduct(_DerivedHandle):

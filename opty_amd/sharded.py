@@ -39,6 +39,19 @@ evaluation itself:
                     one page-locked host vector shared by all processes
                     (:class:`SharedHostVector`) -- 8 links in parallel instead
                     of funnelling 792 MB through one GPU.
+
+The matrix-free products ``J(free) v`` and ``J(free)^T w`` shard the same way
+(:meth:`ShardedCollocator.jvp` / :meth:`ShardedCollocator.vjp`,
+``opty_hip_jacprod_jvp_shard`` / ``opty_hip_jacprod_vjp_shard``, DESIGN.md
+section 10.2): rank ``g`` computes the rows of ``J v`` that belong to its
+constraint nodes, and the entries of ``J^T w`` at the time nodes it OWNS --
+``[a_g, b_g)``, the last rank also node ``N - 1`` -- from the global ``free``
+and the global vector; entry ``p`` needs constraint node ``p - 1`` too, so a
+window starts one (halo) node early.  Both have the bits of the
+whole-problem products.  The node-invariant tail of ``J^T w`` (unknown
+parameters, a free ``h``) is a sum over all constraint nodes: every rank
+returns its share, and whoever assembles the vector adds the shares in rank
+order.
 """
 
 import os
@@ -284,6 +297,12 @@ class ShardedCollocator(object):
     ``instance_evaluator``: ``g(free, con_tail, jac_tail)`` (either may be
     None); ``block_shape`` is checked against the problem's ``(M, P)``.
 
+    ``product_evaluator``: ``(jvp_f, vjp_f)`` in place of the HIP product
+    kernels (:meth:`jvp` / :meth:`vjp`; CPU tests): ``jvp_f(free, v, out2d,
+    inst_out, a, b)`` fills the ``(M, b - a)`` block and, where ``inst_out``
+    is not None, the ``o`` instance rows; ``vjp_f(free, w, out2d, tail_part,
+    a, b)`` fills the ``(n + q, owned)`` block and the ``r + s`` tail shares.
+
     The known maps are re-read on every :meth:`evaluate` (the reference reads
     them on every call, ``opty/direct_collocation.py:2891-2926``), callable
     known trajectories are evaluated on the host from ``free``.
@@ -296,7 +315,8 @@ class ShardedCollocator(object):
                  known_parameter_map={}, known_trajectory_map={},
                  instance_constraints=None, rank=None, world_size=None,
                  group=None, device=None, evaluator=None, block_shape=None,
-                 instance_evaluator=None, comm=None, **kwargs):
+                 instance_evaluator=None, comm=None, product_evaluator=None,
+                 **kwargs):
         import torch
         #: ``hip_backend.HipComm`` (or None): when given -- and the HIP
         #: evaluator is in use -- :meth:`broadcast_free` and :meth:`gather` go
@@ -364,6 +384,12 @@ class ShardedCollocator(object):
             self.device = torch.device(device or 'cpu')
         self._evaluate = evaluator
         self._evaluate_instance = instance_evaluator
+        if self._hip_mode:
+            product_evaluator = (self._hip_jvp, self._hip_vjp)
+        self._products = product_evaluator
+        #: buffers of the products (allocated by the first product)
+        self.jv_local = self.jv_inst = self.jtw_local = self.tail_part = None
+        self._product_handle = None
         cnt = self.b - self.a
         f64 = dict(dtype=torch.float64, device=self.device)
         self.con_local = torch.empty((self.M, cnt), **f64)
@@ -591,6 +617,147 @@ class ShardedCollocator(object):
 
     def _num_free(self):
         return self.collocator.num_free
+
+    # -- matrix-free products (no collective) --------------------------------------
+    @property
+    def owned_nodes(self):
+        """``(lo, hi)``: the time nodes whose entries of ``J^T w`` this rank
+        computes -- its constraint nodes' and, on the last rank, node ``N -
+        1``.  The ranges of all ranks tile ``[0, N)``."""
+        return self.a, self.b + (1 if self.b == self.N - 1 else 0)
+
+    def _product_buffers(self):
+        """The rank-local results of the products, allocated on first use (a
+        collocator that is never asked for products holds none)."""
+        if self.jv_local is None:
+            import torch
+            col = self.collocator
+            f64 = dict(dtype=torch.float64, device=self.device)
+            #: ``r + s`` node-invariant entries end the free vector; ``n + q``
+            #: trajectory rows of ``N`` entries precede them
+            self.num_tail = len(col.unknown_parameters) + \
+                int(bool(col._variable_duration))
+            self.num_rows = (col.num_free - self.num_tail)//self.N
+            lo, hi = self.owned_nodes
+            self.jv_local = torch.empty((self.M, self.b - self.a), **f64)
+            self.jv_inst = torch.empty(self.o, **f64)
+            self.jtw_local = torch.empty((self.num_rows, hi - lo), **f64)
+            self.tail_part = torch.empty(self.num_tail, **f64)
+
+    def _hip_products(self):
+        """The product handle of the global problem (built and verified on
+        first use); what :meth:`set_known` installed last stays installed."""
+        if self._product_handle is None:
+            self._use_stream()
+            self._product_handle = self.collocator._ensure_jacprod()
+            # (the verification evaluated this rank's own maps)
+            if self.known_parameters is not None or \
+                    self.known_trajectories is not None:
+                self.set_known(self.known_parameters, self.known_trajectories)
+        return self._product_handle
+
+    def _hip_jvp(self, free, v, out2d, inst_out, a, b):
+        handle = self._hip_products()
+        self._use_stream()
+        handle.jvp_shard(free, v, out2d, out2d.stride(0), a, b)
+        if inst_out is not None:
+            handle.jvp_instance(free, v, inst_out)
+
+    def _hip_vjp(self, free, w, out2d, tail_part, a, b):
+        handle = self._hip_products()
+        self._use_stream()
+        handle.vjp_shard(free, w, out2d, out2d.stride(0),
+                         tail_part if tail_part.numel() else None, a, b)
+
+    def _check_product(self, free, vec, count, name):
+        if self._products is None:
+            raise ValueError('a collocator with an injected evaluator needs '
+                             'product_evaluator for the products')
+        if free.numel() != self._num_free():
+            raise ValueError('free must have {} entries, got {}'.format(
+                self._num_free(), free.numel()))
+        if vec.numel() != count:
+            raise ValueError('{} must have {} entries, got {}'.format(
+                name, count, vec.numel()))
+
+    def jvp(self, free, v, sync=True):
+        """This rank's rows of ``J(free) v`` from the global ``free`` and the
+        global ``v`` (``num_free`` doubles, on this rank's device): ``(block,
+        inst)`` -- ``block`` is ``(M, b - a)``, row ``j`` = equation ``j`` at
+        the rank's constraint nodes, bit for bit the whole-problem product's
+        ``[j*(N-1) + a, j*(N-1) + b)``; ``inst`` the ``o`` instance rows on
+        :attr:`tail_rank`, None elsewhere.  Buffers of this object, which the
+        next call overwrites.  ``sync`` as in :meth:`evaluate`.  Block
+        products are not sharded."""
+        self._check_product(free, v, self._num_free(), 'v')
+        self._product_buffers()
+        if self._hip_mode:
+            self._hip_products()
+        if sync:
+            self.sync_known(free)
+        inst = self.jv_inst if (self.o and self.rank == self.tail_rank) \
+            else None
+        self._products[0](free, v, self.jv_local, inst, self.a, self.b)
+        return self.jv_local, inst
+
+    def vjp(self, free, w, sync=True):
+        """This rank's entries of ``J(free)^T w`` from the global ``free`` and
+        the global ``w`` (``num_constraints`` doubles): ``(block,
+        tail_part)`` -- ``block`` is ``(n + q, owned)``, row ``R`` = the
+        entries ``[R*N + lo, R*N + hi)`` of the whole-problem product, bit
+        for bit (:attr:`owned_nodes`; the instance constraints' terms of the
+        atoms at owned nodes included); ``tail_part`` this rank's share of
+        the ``r + s`` node-invariant entries, the sum over its constraint
+        nodes.  The entries themselves are the sum of the ranks' shares IN
+        RANK ORDER (:meth:`sum_tail_parts`)."""
+        self._check_product(free, w, self.num_constraints, 'w')
+        self._product_buffers()
+        if self._hip_mode:
+            self._hip_products()
+        if sync:
+            self.sync_known(free)
+        self._products[1](free, w, self.jtw_local, self.tail_part, self.a,
+                          self.b)
+        return self.jtw_local, self.tail_part
+
+    def products_to_host(self, jv_host=None, jtw_host=None, tails_host=None):
+        """Copies the last :meth:`jvp` into the node-wide host vector
+        ``jv_host`` (``M*(N-1) + o`` doubles: row ``j`` to ``[j*(N-1) + a,
+        j*(N-1) + b)``, the instance rows by :attr:`tail_rank`) and / or the
+        last :meth:`vjp` into ``jtw_host`` (``num_free`` doubles: row ``R`` to
+        ``[R*N + lo, R*N + hi)``) and its tail shares into row ``rank`` of
+        ``tails_host`` (``world_size*(r + s)`` doubles); all
+        :class:`SharedHostVector`.  Enqueued on the current stream:
+        synchronise it before reading.  The tail of ``jtw_host`` is for the
+        assembling rank to fill (:meth:`sum_tail_parts`)."""
+        ncn = self.N - 1
+        if jv_host is not None:
+            jv_host.torch_view(0, self.M*ncn).view(
+                self.M, ncn)[:, self.a:self.b].copy_(self.jv_local,
+                                                     non_blocking=True)
+            if self.o and self.rank == self.tail_rank:
+                jv_host.torch_view(self.M*ncn, self.num_constraints).copy_(
+                    self.jv_inst, non_blocking=True)
+        if jtw_host is not None:
+            lo, hi = self.owned_nodes
+            R = self.num_rows
+            jtw_host.torch_view(0, R*self.N).view(R, self.N)[:, lo:hi].copy_(
+                self.jtw_local, non_blocking=True)
+            if self.num_tail:
+                T = self.num_tail
+                tails_host.torch_view(self.rank*T, (self.rank + 1)*T).copy_(
+                    self.tail_part, non_blocking=True)
+
+    @staticmethod
+    def sum_tail_parts(parts):
+        """The node-invariant tail of ``J^T w`` from the ``(world, r + s)``
+        array of the ranks' shares: added one rank after the other, in rank
+        order -- the same bits whoever adds them."""
+        parts = np.asarray(parts)
+        total = np.array(parts[0])
+        for g in range(1, parts.shape[0]):
+            total = total + parts[g]
+        return total
 
     def broadcast_free(self, free, src=0):
         """RCCL broadcast of the global free vector from rank ``src`` (18 MB
@@ -847,9 +1014,19 @@ class ShardedCallbacks(object):
     reference does (``:2891-2926``), and values that changed -- and the values
     of callable known trajectories, evaluated on the root from ``free``
     (``:2916-2917``) -- are broadcast with the command.
+
+    :meth:`jvp` / :meth:`vjp` serve the matrix-free products ``J(free) v`` /
+    ``J(free)^T w`` the same way: the vector takes
+    the route ``free`` takes, every rank evaluates its window
+    (:meth:`ShardedCollocator.jvp` / :meth:`ShardedCollocator.vjp`) and
+    copies its slices into shared host vectors -- under both backends: a
+    result is ``num_free`` doubles at the most -- and the root adds the
+    ranks' shares of the node-invariant tail of ``J^T w`` in rank order.  The
+    vectors of the products are created by the first product command.  Block
+    products and the Hessian are not sharded.
     """
 
-    _STOP, _CON, _JAC, _BOTH = 0, 1, 2, 3
+    _STOP, _CON, _JAC, _BOTH, _JVP, _VJP = 0, 1, 2, 3, 4, 5
 
     def __init__(self, sharded, name=None, root=0, pin=True,
                  fresh_constraints=True, jac_host=None):
@@ -907,6 +1084,10 @@ class ShardedCallbacks(object):
         self._sent_params = self._sent_traj = None
         self._pending = self._con_dev = None
         self._dist = dist
+        # the products' vectors: made by the first product command
+        self._name, self._pin, self._shm = name, pin, shm
+        self._pending_vec = self._vec_dev = None
+        self.vec_host = self.jv_host = self.jtw_host = self.tails_host = None
 
     # -- one evaluation, on every rank ------------------------------------------
     def _known_updates(self, free):
@@ -942,10 +1123,10 @@ class ShardedCallbacks(object):
             sh.set_known(traj=self._traj_buf if self._rccl
                          else self._traj_buf.numpy())
 
-    def _round(self, cmd, flags, params=None, traj=None):
+    def _load_free(self):
+        """``free`` reaches every rank's GPU: broadcast GPU to GPU under
+        RCCL, from the shared host vector under gloo."""
         import torch
-        what = {self._CON: 'con', self._JAC: 'jac', self._BOTH: 'both'}[cmd]
-        self._share_known(flags, params, traj)
         if self._rccl:
             if self.is_root:
                 self.free_dev.copy_(torch.from_numpy(self._pending))
@@ -954,6 +1135,69 @@ class ShardedCallbacks(object):
         else:
             self.free_dev.copy_(self.free_host.torch_view(),
                                 non_blocking=True)
+
+    def _product_vectors(self):
+        """The vectors of the products, on every rank in the same round (their
+        creation is collective): the direction on the device and, under
+        gloo, in shared host memory; the results and the ranks' tail shares
+        in shared host memory."""
+        if self.jv_host is not None:
+            return
+        import torch
+        sh = self.sh
+        sh._product_buffers()
+        nfree, ncon = self.num_free, sh.num_constraints
+        self._vec_dev = torch.empty(max(nfree, ncon), dtype=torch.float64,
+                                    device=sh.device)
+        kw = dict(pin=self._pin, **self._shm)
+        if not self._rccl:
+            self.vec_host = SharedHostVector(self._name + '_vec',
+                                             max(nfree, ncon), sh.rank, **kw)
+        self.jv_host = SharedHostVector(self._name + '_jv', ncon, sh.rank,
+                                        **kw)
+        self.jtw_host = SharedHostVector(self._name + '_jtw', nfree, sh.rank,
+                                         **kw)
+        self.tails_host = SharedHostVector(
+            self._name + '_tails', max(1, sh.world_size*sh.num_tail), sh.rank,
+            **kw)
+
+    def _product_round(self, cmd, flags, params=None, traj=None):
+        import torch
+        sh = self.sh
+        self._product_vectors()
+        self._share_known(flags, params, traj)
+        self._load_free()
+        count = self.num_free if cmd == self._JVP else sh.num_constraints
+        vec = self._vec_dev[:count]
+        if self._rccl:
+            if self.is_root:
+                vec.copy_(torch.from_numpy(self._pending_vec))
+            self._dist.broadcast(vec, self.root, group=sh.group)
+        else:
+            # the shared vector may be this round's: the root fills it here,
+            # and nobody reads it before the root has
+            if self.is_root:
+                self.vec_host.array[:count] = self._pending_vec
+            self._dist.barrier(sh.group)
+            vec.copy_(self.vec_host.torch_view(0, count), non_blocking=True)
+        if cmd == self._JVP:
+            sh.jvp(self.free_dev, vec, sync=False)
+            sh.products_to_host(jv_host=self.jv_host)
+        else:
+            sh.vjp(self.free_dev, vec, sync=False)
+            sh.products_to_host(jtw_host=self.jtw_host,
+                                tails_host=self.tails_host)
+        if sh.device.type == 'cuda':
+            torch.cuda.synchronize(sh.device)
+        self._dist.barrier(sh.group)            # every slice has landed
+
+    def _round(self, cmd, flags, params=None, traj=None):
+        import torch
+        if cmd in (self._JVP, self._VJP):
+            return self._product_round(cmd, flags, params, traj)
+        what = {self._CON: 'con', self._JAC: 'jac', self._BOTH: 'both'}[cmd]
+        self._share_known(flags, params, traj)
+        self._load_free()
         self.sh.evaluate(self.free_dev, what=what, sync=False)
         if what != 'jac':
             if self._rccl:
@@ -978,13 +1222,21 @@ class ShardedCallbacks(object):
         return int(got[0]), (int(got[1]), int(got[2]))
 
     # -- the solver's side (rank `root`) -------------------------------------------
-    def _call(self, free, cmd):
+    def _call(self, free, cmd, vec=None, name=None):
         assert self.is_root, 'callbacks run on the root rank; others serve()'
         free = np.ascontiguousarray(free, dtype=np.float64)
         if free.shape != (self.num_free,):
             raise ValueError('free must have shape ({},), got {}'.format(
                 self.num_free, free.shape))
+        if vec is not None:
+            count = self.num_free if cmd == self._JVP else \
+                self.sh.num_constraints
+            vec = np.ascontiguousarray(vec, dtype=np.float64)
+            if vec.shape != (count,):
+                raise ValueError('{} must have shape ({},), got {}'.format(
+                    name, count, vec.shape))
         params, traj = self._known_updates(free)
+        self._pending_vec = vec
         if self._rccl:
             self._pending = free
         else:
@@ -992,7 +1244,7 @@ class ShardedCallbacks(object):
         flags = (int(params is not None), int(traj is not None))
         self._command(cmd, flags)
         self._round(cmd, flags, params, traj)
-        self._pending = None
+        self._pending = self._pending_vec = None
 
     def _constraints_result(self):
         if self._rccl:
@@ -1012,6 +1264,27 @@ class ShardedCallbacks(object):
     def constraints_and_jacobian(self, free):
         self._call(free, self._BOTH)
         return self._constraints_result(), self.jac_host.array
+
+    def jvp(self, free, v):
+        """``J(free) v`` (``num_constraints`` doubles, ordered like
+        ``constraints(free)``; a fresh array), every rank's rows bit for bit
+        those of the single-GPU product."""
+        self._call(free, self._JVP, v, 'v')
+        return np.array(self.jv_host.array)
+
+    def vjp(self, free, w):
+        """``J(free)^T w`` (``num_free`` doubles, ordered like ``free``; a
+        fresh array): the trajectory entries bit for bit those of the
+        single-GPU product, the node-invariant tail the sum of the ranks'
+        shares in rank order."""
+        self._call(free, self._VJP, w, 'w')
+        sh = self.sh
+        out = np.array(self.jtw_host.array)
+        if sh.num_tail:
+            parts = self.tails_host.array[:sh.world_size*sh.num_tail]
+            out[sh.num_rows*sh.N:] = sh.sum_tail_parts(
+                parts.reshape(sh.world_size, sh.num_tail))
+        return out
 
     def shutdown(self):
         """Releases the serving ranks (root only; idempotent)."""
@@ -1033,6 +1306,8 @@ class ShardedCallbacks(object):
     def close(self):
         self._cmd = None
         for v in (self.free_host, self.con_host,
-                  self.jac_host if self._own_jac_host else None):
+                  self.jac_host if self._own_jac_host else None,
+                  self.vec_host, self.jv_host, self.jtw_host,
+                  self.tails_host):
             if v is not None:
                 v.close()
