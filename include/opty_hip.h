@@ -179,7 +179,8 @@ typedef struct opty_hip_desc {
  * signature of version 12 changed, and a client finds out whether its library
  * has them by looking the symbols up; likewise, later still,
  * opty_hip_jacprod_jvp_shard / opty_hip_jacprod_jvp_instance /
- * opty_hip_jacprod_vjp_shard), and
+ * opty_hip_jacprod_vjp_shard, and then opty_hip_eval_hess_shard /
+ * opty_hip_eval_hess_instance / opty_hip_hessian_indices_range), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -748,6 +749,42 @@ int opty_hip_eval_hess(opty_hip_hessian *h, const double *free,
 /* int64 row / column indices of every hess value, same order. */
 int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
                              int64_t *cols, int32_t mem);
+
+/* ---- node-sharded Hessian: a window of the constraint nodes -------------------
+ * What opty_hip_jacprod_jvp_shard is to J v: the values of the constraint
+ * nodes [node_begin, node_end) of the handle's GLOBAL problem, for a host that
+ * node-shards one problem over several GPUs.  Device pointers only, enqueued
+ * on the problem's stream.  `free` and `lagrange` are the GLOBAL vectors at
+ * full length (num_free resp. num_constraints doubles); the kernels are the
+ * two above, opty_hess launched over the window.
+ *   eval_hess_shard    : hess_shard[(i - node_begin)*PH + e] = hess[i*PH + e],
+ *                        node i of the window: (node_end - node_begin)*PH
+ *                        doubles.  hess_shard = global + node_begin*PH writes
+ *                        in place.
+ *   eval_hess_instance : the nnz_inst instance values hess[(N-1)*PH + t] into
+ *                        inst_out; by whichever rank assembles the vector.
+ *                        Succeeds and writes nothing when nnz_inst == 0.
+ *   indices_range      : the global row / column indices of a window's values
+ *                        ((node_end - node_begin)*PH each, in `mem` memory).
+ * Contract: a node's entries depend on that node's inputs and multipliers
+ * alone and the triplets ADD, so there is no halo node and no sum across
+ * windows: every value of every window has the BITS of opty_hip_eval_hess,
+ * for any partition, and nothing outside the window's slice is written.  An
+ * empty window succeeds and launches nothing.  Refused before anything is
+ * enqueued, with the offending number in opty_hip_last_error(): null
+ * pointers, node_begin < 0, node_end > N-1, node_begin > node_end, and, when
+ * PH is even, a hess_shard that is not 16-byte aligned (every in-place window
+ * base is aligned whenever the global base is; an odd PH is written with
+ * 8-byte stores and needs a double's alignment only). */
+int opty_hip_eval_hess_shard(opty_hip_hessian *h, const double *free,
+                             const double *lagrange, double *hess_shard,
+                             int64_t node_begin, int64_t node_end);
+int opty_hip_eval_hess_instance(opty_hip_hessian *h, const double *free,
+                                const double *lagrange,
+                                double *inst_out /* nnz_inst doubles */);
+int opty_hip_hessian_indices_range(opty_hip_hessian *h, int64_t node_begin,
+                                   int64_t node_end, int64_t *rows,
+                                   int64_t *cols, int32_t mem);
 
 /* ---- matrix-free Jacobian products ------------------------------------------
  * J is the matrix of opty_hip_jacobian_indices + opty_hip_eval_jac: shape

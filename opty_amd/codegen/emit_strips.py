@@ -99,16 +99,22 @@ def column_leaf(prog, source=node_input, vec='vec%d'):
     return leaf
 
 
-def block_preamble(stride=64):
+def block_preamble(stride=64, window=False):
     """First lines of a kernel whose block ``blockIdx.x`` holds the 64
     constraint nodes from ``i0 = stride*blockIdx.x`` on: ``i`` the lane's
-    node, ``ic`` the same clamped to the last one."""
+    node, ``ic`` the same clamped to the last one.  ``window``: the kernel
+    evaluates the nodes ``[wa, wb)`` of the global problem (two wave-uniform
+    kernel arguments: scalar registers) -- blocks count from ``wa``, end at
+    ``wb``, and ``ic`` is clamped into the window; ``i`` and ``ic`` stay
+    GLOBAL node indices."""
+    first, end = ('wa + ', 'wb') if window else ('', 'ncn')
     return ['const int lane = threadIdx.x;',
             'const long long ncn = N - 1;',
-            'const long long i0 = (long long)blockIdx.x*%d;' % stride,
-            'if (i0 >= ncn) return;',
+            'const long long i0 = %s(long long)blockIdx.x*%d;' % (first,
+                                                                  stride),
+            'if (i0 >= %s) return;' % end,
             'const long long i = i0 + lane;',
-            'const long long ic = i < ncn ? i : ncn - 1;']
+            'const long long ic = i < %s ? i : %s - 1;' % (end, end)]
 
 
 def strip_switch(lines, bodies):

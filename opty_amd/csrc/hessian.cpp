@@ -7,7 +7,9 @@
 // and what opty_hip_set_known_* installs is what the next call reads.  The
 // generated code object exports `opty_hess` (lane = constraint node, grid.y =
 // strips of the per-node entries) and `opty_hess_inst` (one lane, the
-// instance constraints' entries after the node blocks).
+// instance constraints' entries after the node blocks).  Both take a window
+// [wa, wb) of the constraint nodes: the whole problem is [0, N-1), a rank of a
+// node-sharded problem launches its own (opty_hip_eval_hess_shard).
 #include "opty_internal.h"
 
 #include <cstdint>
@@ -27,8 +29,10 @@ struct HessArgs {
     double *hess;
     double h;
     long long N;
+    long long wa, wb;   // the window of constraint nodes; hess: its first node
+    double *tail;       // opty_hess_inst: the nnz_inst instance entries
 };
-static_assert(sizeof(HessArgs) == 64, "HessArgs must match HESS_PARAMS");
+static_assert(sizeof(HessArgs) == 88, "HessArgs must match HESS_PARAMS");
 
 // Closed-form indices: entry e of constraint node i has the global indices
 // side(pattern[4e], pattern[4e+1]) and side(pattern[4e+2], pattern[4e+3]),
@@ -39,14 +43,19 @@ __global__ void __launch_bounds__(256)
 opty_hess_indices_kernel(const int *pattern, int PH, long long N,
                          long long ncn, long long tail, const long long *irows,
                          const long long *icols, int nnz_inst,
-                         long long *rows, long long *cols) {
-    const long long i = blockIdx.x;
-    if (i < ncn) {
+                         long long *rows, long long *cols, long long wa,
+                         long long wb) {
+    // [wa, wb): the window of nodes; rows / cols start at its first node.
+    // The instance block exists in the whole-problem launch only (wb == ncn,
+    // wa == 0), one block past the nodes.
+    const long long i = wa + blockIdx.x;
+    if (i < wb) {
+        const long long at = (i - wa)*PH;
         for (int e = threadIdx.x; e < PH; e += blockDim.x) {
             const int ra = pattern[4*e], oa = pattern[4*e + 1];
             const int rb = pattern[4*e + 2], ob = pattern[4*e + 3];
-            rows[i*PH + e] = ra >= 0 ? (long long)ra*N + i + oa : tail + oa;
-            cols[i*PH + e] = rb >= 0 ? (long long)rb*N + i + ob : tail + ob;
+            rows[at + e] = ra >= 0 ? (long long)ra*N + i + oa : tail + oa;
+            cols[at + e] = rb >= 0 ? (long long)rb*N + i + ob : tail + ob;
         }
     } else {
         for (int t = threadIdx.x; t < nnz_inst; t += blockDim.x) {
@@ -69,6 +78,49 @@ struct opty_hip_hessian : Borrowed {
     int64_t ncn() const { return p->d.N - 1; }
     int64_t nnz() const { return (int64_t)d.PH*ncn() + d.nnz_inst; }
 };
+
+namespace {
+
+// Enqueues opty_hess over the window [wa, wb) -- `hess`: the entries of node
+// wa -- and / or opty_hess_inst into `tail` (null: not launched).
+int launch_hess(opty_hip_hessian *h, const double *free_, const double *lam,
+                double *hess, long long wa, long long wb, double *tail) {
+    HessArgs a{};
+    borrowed_args(&a, h->p, free_);
+    a.lam = lam;
+    a.hess = hess;
+    a.wa = wa;
+    a.wb = wb;
+    a.tail = tail;
+    size_t size = sizeof a;
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
+                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
+                      HIP_LAUNCH_PARAM_END};
+    const long long nblk = (wb - wa + 63)/64;
+    if (h->d.PH > 0 && nblk > 0)
+        HIP_TRY(hipModuleLaunchKernel(h->k_hess, (unsigned)nblk,
+                                      (unsigned)h->d.strips, 1, 64, 1, 1, 0,
+                                      h->stream, nullptr, config));
+    if (h->d.nnz_inst > 0 && tail)
+        HIP_TRY(hipModuleLaunchKernel(h->k_inst, 1, 1, 1, 64, 1, 1, 0,
+                                      h->stream, nullptr, config));
+    return 0;
+}
+
+// The window check of the windowed entry points: the offending number is in
+// the message.
+int check_hess_window(const opty_hip_hessian *h, int64_t a, int64_t b) {
+    if (a < 0) return fail("node_begin %lld < 0", (long long)a);
+    if (b > h->ncn())
+        return fail("node_end %lld > the %lld constraint nodes",
+                    (long long)b, (long long)h->ncn());
+    if (a > b)
+        return fail("node_begin %lld > node_end %lld", (long long)a,
+                    (long long)b);
+    return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -153,30 +205,21 @@ int opty_hip_eval_hess(opty_hip_hessian *h, const double *free_,
     const long long ncn = h->ncn();
     const size_t nfree = (size_t)p->num_free(), ncon = (size_t)p->num_con(),
                  nnz = (size_t)h->nnz();
-    HessArgs a{};
-    a.lam = lagrange;
-    a.hess = hess;
+    const double *lam = lagrange;
+    double *dhess = hess;
     if (mem == OPTY_HIP_HOST) {
         if (int rc = stage_in(h, &free_, &h->d_free, nfree, nfree)) return rc;
-        if (int rc = stage_in(h, &a.lam, &h->d_lam, ncon,
+        if (int rc = stage_in(h, &lam, &h->d_lam, ncon,
                               std::max<size_t>(1, ncon)))
             return rc;
         if (int rc = ensure(&h->d_hess, std::max<size_t>(1, nnz))) return rc;
-        a.hess = h->d_hess;
+        dhess = h->d_hess;
     }
-    borrowed_args(&a, p, free_);
-    size_t size = sizeof a;
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a,
-                      HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
-                      HIP_LAUNCH_PARAM_END};
-    const long long nblk = (ncn + 63)/64;
-    if (h->d.PH > 0 && nblk > 0)
-        HIP_TRY(hipModuleLaunchKernel(h->k_hess, (unsigned)nblk,
-                                      (unsigned)h->d.strips, 1, 64, 1, 1, 0,
-                                      h->stream, nullptr, config));
-    if (h->d.nnz_inst > 0)
-        HIP_TRY(hipModuleLaunchKernel(h->k_inst, 1, 1, 1, 64, 1, 1, 0,
-                                      h->stream, nullptr, config));
+    // the whole problem: every constraint node, the instance entries behind
+    // the node blocks
+    if (int rc = launch_hess(h, free_, lam, dhess, 0, ncn,
+                             dhess + (size_t)ncn*(size_t)h->d.PH))
+        return rc;
     if (mem == OPTY_HIP_HOST) {
         if (int rc = stage_out(h, hess, h->d_hess, nnz*sizeof(double)))
             return rc;
@@ -205,9 +248,73 @@ int opty_hip_hessian_indices(opty_hip_hessian *h, int64_t *rows,
         hipLaunchKernelGGL(opty_hess_indices_kernel, dim3((unsigned)blocks),
                            dim3(256), 0, h->stream, h->d_pattern, h->d.PH,
                            (long long)p->d.N, ncn, tail, h->d_irows,
-                           h->d_icols, h->d.nnz_inst, dr, dc);
+                           h->d_icols, h->d.nnz_inst, dr, dc, 0LL, ncn);
         HIP_TRY(hipGetLastError());
     }
+    if (mem == OPTY_HIP_HOST) {
+        if (int rc = stage_out(h, rows, h->d_rows, nnz*sizeof(long long)))
+            return rc;
+        if (int rc = stage_out(h, cols, h->d_cols, nnz*sizeof(long long)))
+            return rc;
+        return host_done(h);
+    }
+    return 0;
+}
+
+int opty_hip_eval_hess_shard(opty_hip_hessian *h, const double *free_,
+                             const double *lagrange, double *hess_shard,
+                             int64_t node_begin, int64_t node_end) {
+    if (!h || !free_ || !lagrange || !hess_shard)
+        return fail("null argument");
+    if (int rc = check_hess_window(h, node_begin, node_end)) return rc;
+    // an even PH: 16-byte stores at hess_shard + (even offset); every in-place
+    // window base global + node_begin*PH is aligned when the global base is
+    if (h->d.PH > 0 && h->d.PH % 2 == 0 &&
+        (reinterpret_cast<uintptr_t>(hess_shard) & 15) != 0)
+        return fail("hess_shard (%p) must be 16-byte aligned in device memory "
+                    "when PH (%d) is even", (void *)hess_shard, h->d.PH);
+    if (int rc = borrowed_begin(h, OPTY_HIP_DEVICE, true)) return rc;
+    if (node_begin == node_end) return 0;
+    return launch_hess(h, free_, lagrange, hess_shard, node_begin, node_end,
+                       nullptr);
+}
+
+int opty_hip_eval_hess_instance(opty_hip_hessian *h, const double *free_,
+                                const double *lagrange, double *inst_out) {
+    if (!h || !free_ || !lagrange) return fail("null argument");
+    if (h->d.nnz_inst == 0) return 0;
+    if (!inst_out) return fail("null argument");
+    if (int rc = borrowed_begin(h, OPTY_HIP_DEVICE, true)) return rc;
+    return launch_hess(h, free_, lagrange, nullptr, 0, 0, inst_out);
+}
+
+int opty_hip_hessian_indices_range(opty_hip_hessian *h, int64_t node_begin,
+                                   int64_t node_end, int64_t *rows,
+                                   int64_t *cols, int32_t mem) {
+    if (!h || !rows || !cols) return fail("null argument");
+    if (int rc = check_hess_window(h, node_begin, node_end)) return rc;
+    if (int rc = borrowed_begin(h, mem, false)) return rc;
+    opty_hip_problem *p = h->p;
+    const long long count = node_end - node_begin;
+    const size_t nnz = (size_t)count*(size_t)h->d.PH;
+    if (nnz == 0) return 0;
+    long long *dr = (long long *)rows, *dc = (long long *)cols;
+    if (mem == OPTY_HIP_HOST) {
+        // (the staging vectors of opty_hip_hessian_indices: the whole
+        // problem's size, which no window exceeds)
+        const size_t all = std::max<size_t>(1, (size_t)h->nnz());
+        if (int rc = ensure(&h->d_rows, all)) return rc;
+        if (int rc = ensure(&h->d_cols, all)) return rc;
+        dr = h->d_rows;
+        dc = h->d_cols;
+    }
+    const long long tail = (long long)(p->d.n + p->d.q)*p->d.N;
+    hipLaunchKernelGGL(opty_hess_indices_kernel, dim3((unsigned)count),
+                       dim3(256), 0, h->stream, h->d_pattern, h->d.PH,
+                       (long long)p->d.N, (long long)h->ncn(), tail,
+                       h->d_irows, h->d_icols, 0, dr, dc,
+                       (long long)node_begin, (long long)node_end);
+    HIP_TRY(hipGetLastError());
     if (mem == OPTY_HIP_HOST) {
         if (int rc = stage_out(h, rows, h->d_rows, nnz*sizeof(long long)))
             return rc;

@@ -3739,26 +3739,116 @@ class ShardedProblem(Problem):
     not sharded.
 
     :meth:`jacobian_operator` gives the matrix-free products ``J v`` / ``J^T
-    w`` of the sharded problem; block products, the Hessian
-    (``obj_hessian``, :meth:`hessian_operator`) and ``ufuncify_matrix`` are
+    w`` of the sharded problem; block products and ``ufuncify_matrix`` are
     not sharded.
 
+    ``obj_hessian=(rows, cols, values)`` (``Problem``'s argument, with its
+    checks) gives the root the two callbacks of the exact Hessian
+    (DESIGN.md section 9.2): ``hessianstructure()`` is the ``[constraint |
+    objective]`` structure of ``Problem``, and in ``hessian(free, lagrange,
+    obj_factor)`` every rank evaluates the constraint triplets of its own
+    nodes (:meth:`opty_amd.sharded.ShardedCallbacks.hessian`: every value has
+    the bits of the single-GPU ``Problem.hessian``) while the root alone
+    evaluates the objective's -- on its GPU when ``values.handle`` is a
+    ``HipObjectiveHessian`` -- behind them in the same shared host vector,
+    which is returned and overwritten by the next call.  Host arrays only.
+    ``values`` is only ever called on the root.  What
+    ``generate_hessian_function`` refuses (implicit known trajectories,
+    known trajectories given as functions of ``free``) is refused by the
+    constructor on every rank, before any collective; so is ``obj_hessian``
+    in a process without an initialised ``torch.distributed`` group
+    (``NotImplementedError``: there are no ranks to serve it).  Not sharded:
+    ``H v``
+    from shards that stay in device memory (:meth:`hessian_operator`
+    refuses), the objective's Hessian, block products; the torch-free host
+    (``shard_host.py``) and the C client do not serve the Hessian.
+
     Extra keywords: ``group`` (process group), ``root`` (solver rank),
-    ``torch_device`` (default ``cuda:<device>``).
+    ``torch_device`` (default ``cuda:<device>``), ``sharded_kwargs`` (further
+    keywords of :class:`opty_amd.sharded.ShardedCollocator`: the evaluators
+    the CPU tests inject).
     """
 
     def __init__(self, *args, group=None, root=0, torch_device=None,
-                 **kwargs):
-        if kwargs.get('obj_hessian') is not None:
-            raise NotImplementedError('the Hessian is not sharded: '
-                                      'ShardedProblem takes no obj_hessian.')
+                 sharded_kwargs=None, **kwargs):
         self._group, self._root, self._torch_device = group, root, \
             torch_device
+        self._sharded_kwargs = dict(sharded_kwargs or {})
+        self._with_hessian = kwargs.get('obj_hessian') is not None
+        if self._with_hessian:
+            # the first of the refusals that come before any collective: the
+            # sharded Hessian is what the ranks of a process group evaluate
+            # on the root's command, and without a group there are none
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()):
+                raise NotImplementedError(
+                    'the Hessian of a ShardedProblem is evaluated by the '
+                    'ranks of a torch.distributed process group, and none '
+                    'is initialised: there is nothing to shard over.  Use '
+                    'Problem(obj_hessian=...) in a single process.')
         super().__init__(*args, **kwargs)
 
     def hessian_operator(self, free, lagrange, obj_factor=1.0):
         raise NotImplementedError('the Hessian is not sharded: '
                                   'ShardedProblem has no hessian_operator.')
+
+    def _install_hessian(self, obj_hessian):
+        """``hessianstructure()`` and ``hessian(free, lagrange,
+        obj_factor)`` of :meth:`Problem._install_hessian`, the constraint
+        section served by all ranks.  Every rank gets here (the size of the
+        shared vector is agreed without communication); only the root holds
+        the structure and ever calls ``values``."""
+        rows, cols, values = obj_hessian
+        if np.any((rows < 0) | (rows >= self.num_free)):
+            raise ValueError('obj_hessian indices out of range.')
+        cb, col = self.callbacks, self.collocator
+        cb.hessian_extra = len(rows)
+        if not cb.is_root:
+            return
+        num_con = self.sharded.hessian_nnz
+        # (the closed form on the host: the device's index kernel is held to
+        # it by the tests, and the root need not build its handle for it)
+        crows, ccols = col.hessian_indices_closed_form()
+        assert len(crows) == num_con
+        structure = (np.concatenate((crows, rows)),
+                     np.concatenate((ccols, cols)))
+        nargs = values.__code__.co_argcount - len(values.__defaults__ or ()) \
+            if hasattr(values, '__code__') else 1
+        on_device = isinstance(getattr(values, 'handle', None),
+                               hb.HipObjectiveHessian)
+        obj_dev = []
+
+        def hessianstructure():
+            return structure
+
+        def hessian(free, lagrange, obj_factor):
+            if hasattr(free, 'data_ptr') or hasattr(lagrange, 'data_ptr'):
+                raise TypeError(
+                    'ShardedProblem.hessian takes host arrays only: the '
+                    'result is assembled in a host vector shared by the '
+                    'ranks, not in one GPU\'s memory; pass NumPy arrays '
+                    '(free.cpu().numpy()).')
+            free = np.ascontiguousarray(free, dtype=np.float64)
+            out = cb.hessian(free, lagrange)
+            if not len(rows):
+                return out
+            if on_device:
+                # the root's own GPU, into the (page-locked) shared vector
+                # behind the constraint section
+                import torch
+                if not obj_dev:
+                    obj_dev.append(torch.empty(
+                        len(rows), dtype=torch.float64,
+                        device=self.sharded.device))
+                values(cb.free_dev, obj_factor, obj_dev[0])
+                cb.hess_host.torch_view(num_con, num_con + len(rows)).copy_(
+                    obj_dev[0])
+                return out
+            v = values(self, free) if nargs == 2 else values(free)
+            out[num_con:] = obj_factor*np.asarray(v, dtype=float)
+            return out
+        self.hessianstructure = hessianstructure
+        self.hessian = hessian
 
     def _make_collocator(self, eom, states, num_nodes, interval, par_map,
                          traj_map, instance_constraints, time_symbol, tmp_dir,
@@ -3768,12 +3858,19 @@ class ShardedProblem(Problem):
         if device is None:
             device = 'cuda:%d' % kwargs.get('device', 0)
         kwargs.pop('device', None)
+        kwargs.update(self._sharded_kwargs)
         self.sharded = ShardedCollocator(
             eom, states, num_nodes, interval, par_map, traj_map,
             instance_constraints, group=self._group, device=device,
             time_symbol=time_symbol, tmp_dir=tmp_dir,
             integration_method=integration_method, parallel=parallel,
             **kwargs)
+        if self._with_hessian:
+            # what generate_hessian_function refuses (implicit known
+            # trajectories, known trajectories as functions of free) is
+            # refused here, on every rank, before the first collective: a
+            # refusal inside one would leave the other ranks waiting
+            self.sharded.collocator._build_hessian_program()
         return self.sharded.collocator
 
     def _make_callbacks(self):

@@ -559,6 +559,11 @@ _SIGNATURES = {
     'opty_hip_hessian_nnz': (ctypes.c_int64, [_P]),
     'opty_hip_eval_hess': (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int32]),
     'opty_hip_hessian_indices': (ctypes.c_int, [_P, _P, _P, ctypes.c_int32]),
+    'opty_hip_eval_hess_shard': (ctypes.c_int, [
+        _P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64]),
+    'opty_hip_eval_hess_instance': (ctypes.c_int, [_P, _P, _P, _P]),
+    'opty_hip_hessian_indices_range': (ctypes.c_int, [
+        _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.c_int32]),
     'opty_hip_jacprod_create': (ctypes.c_int,
                                 [_P, ctypes.POINTER(_JacprodDesc),
                                  ctypes.c_char_p, ctypes.POINTER(_P)]),
@@ -1391,6 +1396,28 @@ class HipHessian(_DerivedHandle):
     def indices(self, rows, cols, mem):
         _check(self._lib.opty_hip_hessian_indices(self._handle(), _ptr(rows),
                                                   _ptr(cols), mem))
+
+    def eval_shard(self, free, lagrange, hess_shard, node_begin, node_end):
+        """The values of the constraint nodes ``[node_begin, node_end)`` from
+        the global device ``free`` / ``lagrange`` into the ``(node_end -
+        node_begin)*PH`` doubles ``hess_shard``; see
+        ``opty_hip_eval_hess_shard`` in ``include/opty_hip.h``."""
+        _check(self._lib.opty_hip_eval_hess_shard(
+            self._handle(), _ptr(free), _ptr(lagrange), _ptr(hess_shard),
+            int(node_begin), int(node_end)))
+
+    def eval_instance(self, free, lagrange, inst_out):
+        """The ``nnz_inst`` instance values into the device buffer
+        ``inst_out`` (``opty_hip_eval_hess_instance``)."""
+        _check(self._lib.opty_hip_eval_hess_instance(
+            self._handle(), _ptr(free), _ptr(lagrange), _ptr(inst_out)))
+
+    def indices_range(self, node_begin, node_end, rows, cols, mem):
+        """Global indices of the values of the nodes ``[node_begin,
+        node_end)`` (``opty_hip_hessian_indices_range``)."""
+        _check(self._lib.opty_hip_hessian_indices_range(
+            self._handle(), int(node_begin), int(node_end), _ptr(rows),
+            _ptr(cols), mem))
 
 
 class HipJacobianProduct(_DerivedHandle):

@@ -52,6 +52,15 @@ whole-problem products.  The node-invariant tail of ``J^T w`` (unknown
 parameters, a free ``h``) is a sum over all constraint nodes: every rank
 returns its share, and whoever assembles the vector adds the shares in rank
 order.
+
+The exact Hessian of the constraint Lagrangian shards without any of that
+(:meth:`ShardedCollocator.hessian`, ``opty_hip_eval_hess_shard``, DESIGN.md
+section 9.2): the values are node-major, ``hess[i*PH + e]``, node ``i``'s
+entries depend on node ``i``'s inputs and multipliers alone, and the triplets
+ADD -- rank ``g`` writes the contiguous slice ``[a_g*PH, b_g*PH)``, there is
+no halo node and no sum across ranks, and every value has the bits of the
+whole-problem evaluation.  The instance entries follow the node blocks and
+are evaluated by :attr:`ShardedCollocator.tail_rank`.
 """
 
 import os
@@ -303,6 +312,11 @@ class ShardedCollocator(object):
     is not None, the ``o`` instance rows; ``vjp_f(free, w, out2d, tail_part,
     a, b)`` fills the ``(n + q, owned)`` block and the ``r + s`` tail shares.
 
+    ``hessian_evaluator``: ``f(free, lagrange, hess1d, inst_out, a, b)`` in
+    place of the HIP Hessian kernels (:meth:`hessian`; CPU tests): fills the
+    ``(b - a)*PH`` values of the window's nodes and, where ``inst_out`` is
+    not None, the ``nnz_inst`` instance values.
+
     The known maps are re-read on every :meth:`evaluate` (the reference reads
     them on every call, ``opty/direct_collocation.py:2891-2926``), callable
     known trajectories are evaluated on the host from ``free``.
@@ -316,7 +330,7 @@ class ShardedCollocator(object):
                  instance_constraints=None, rank=None, world_size=None,
                  group=None, device=None, evaluator=None, block_shape=None,
                  instance_evaluator=None, comm=None, product_evaluator=None,
-                 **kwargs):
+                 hessian_evaluator=None, **kwargs):
         import torch
         #: ``hip_backend.HipComm`` (or None): when given -- and the HIP
         #: evaluator is in use -- :meth:`broadcast_free` and :meth:`gather` go
@@ -390,6 +404,12 @@ class ShardedCollocator(object):
         #: buffers of the products (allocated by the first product)
         self.jv_local = self.jv_inst = self.jtw_local = self.tail_part = None
         self._product_handle = None
+        if self._hip_mode:
+            hessian_evaluator = self._hip_hessian
+        self._hessian = hessian_evaluator
+        #: buffers and handle of the Hessian (made by the first Hessian call)
+        self.hess_local = self.hess_inst = None
+        self._hessian_handle = None
         cnt = self.b - self.a
         f64 = dict(dtype=torch.float64, device=self.device)
         self.con_local = torch.empty((self.M, cnt), **f64)
@@ -759,6 +779,109 @@ class ShardedCollocator(object):
             total = total + parts[g]
         return total
 
+    # -- exact Hessian of the constraint Lagrangian (no collective) ---------------
+    def _hessian_sizes(self):
+        """``PH`` and ``hess_nnz_inst`` -- entries per constraint node / of
+        the instance constraints -- from the Hessian program (lowered and
+        differentiated twice on first use; refused problems raise here)."""
+        if getattr(self, 'PH', None) is None:
+            prog = self.collocator._build_hessian_program()
+            self.PH = prog.PH
+            self.hess_nnz_inst = len(prog.inst_hess_out)
+
+    def _hessian_buffers(self):
+        """The rank-local Hessian values, allocated on first use (a
+        collocator that is never asked for the Hessian holds none)."""
+        if self.hess_local is None:
+            import torch
+            self._hessian_sizes()
+            f64 = dict(dtype=torch.float64, device=self.device)
+            self.hess_local = torch.empty((self.b - self.a)*self.PH, **f64)
+            self.hess_inst = torch.empty(self.hess_nnz_inst, **f64)
+
+    @property
+    def hessian_nnz(self):
+        """``PH*(N-1) + nnz_inst``: length of the global vector of Hessian
+        values (the constraint section of ``Problem.hessian``)."""
+        self._hessian_sizes()
+        return self.PH*(self.N - 1) + self.hess_nnz_inst
+
+    def _hip_hessian_handle(self):
+        """The Hessian handle of the global problem (built and verified on
+        first use); what :meth:`set_known` installed last stays installed."""
+        if self._hessian_handle is None:
+            self._use_stream()
+            self._hessian_handle = self.collocator._ensure_hessian()
+            # (the verification evaluated this rank's own maps)
+            if self.known_parameters is not None or \
+                    self.known_trajectories is not None:
+                self.set_known(self.known_parameters, self.known_trajectories)
+        return self._hessian_handle
+
+    def _hip_hessian(self, free, lagrange, hess1d, inst_out, a, b):
+        handle = self._hip_hessian_handle()
+        self._use_stream()
+        handle.eval_shard(free, lagrange, hess1d, a, b)
+        if inst_out is not None:
+            handle.eval_instance(free, lagrange, inst_out)
+
+    def hessian(self, free, lagrange, sync=True):
+        """This rank's values of the Hessian of the constraint Lagrangian from
+        the global ``free`` and the global ``lagrange`` (``num_constraints``
+        doubles, ordered like ``constraints(free)``; both on this rank's
+        device): ``(values, inst)`` -- ``values`` the slice ``[a*PH, b*PH)``
+        of the whole-problem vector, bit for bit; ``inst`` the ``nnz_inst``
+        instance values on :attr:`tail_rank`, None elsewhere.  Buffers of
+        this object, which the next call overwrites.  ``sync`` as in
+        :meth:`evaluate`.  Lower triangle, triplets that ADD
+        (``ConstraintCollocator.generate_hessian_function``): no rank needs
+        another's values."""
+        if self._hessian is None:
+            raise ValueError('a collocator with an injected evaluator needs '
+                             'hessian_evaluator for the Hessian')
+        if free.numel() != self._num_free():
+            raise ValueError('free must have {} entries, got {}'.format(
+                self._num_free(), free.numel()))
+        if lagrange.numel() != self.num_constraints:
+            raise ValueError('lagrange must have {} entries, got {}'.format(
+                self.num_constraints, lagrange.numel()))
+        self._hessian_buffers()
+        if self._hip_mode:
+            self._hip_hessian_handle()
+        if sync:
+            self.sync_known(free)
+        inst = self.hess_inst if (self.hess_nnz_inst and
+                                  self.rank == self.tail_rank) else None
+        self._hessian(free, lagrange, self.hess_local, inst, self.a, self.b)
+        return self.hess_local, inst
+
+    def hessian_to_host(self, hess_host):
+        """Copies the last :meth:`hessian` into the node-wide host vector
+        ``hess_host`` (a :class:`SharedHostVector` of at least ``PH*(N-1) +
+        nnz_inst`` doubles): the slice to ``[a*PH, b*PH)`` and, on
+        :attr:`tail_rank`, the instance values behind the node blocks.
+        Enqueued on the current stream: synchronise it before reading."""
+        PH, ncn = self.PH, self.N - 1
+        hess_host.torch_view(self.a*PH, self.b*PH).copy_(self.hess_local,
+                                                         non_blocking=True)
+        if self.hess_nnz_inst and self.rank == self.tail_rank:
+            hess_host.torch_view(ncn*PH, ncn*PH + self.hess_nnz_inst).copy_(
+                self.hess_inst, non_blocking=True)
+
+    def hessian_indices_local(self):
+        """Global int64 row and column indices (row >= col) of this rank's
+        Hessian values, from the closed-form index kernel restricted to this
+        rank's nodes.  The instance entries' indices are the tail of
+        ``collocator.hessian_indices_closed_form()``."""
+        from . import hip_backend as hb
+        self._hessian_buffers()
+        handle = self._hip_hessian_handle()
+        count = (self.b - self.a)*self.PH
+        rows = np.empty(count, dtype=np.int64)
+        cols = np.empty(count, dtype=np.int64)
+        handle.indices_range(self.a, self.b, rows, cols, hb.HOST)
+        return rows, cols
+
     def broadcast_free(self, free, src=0):
         """RCCL broadcast of the global free vector from rank ``src`` (18 MB
         for config 4).  The alternative with ``free`` on the host: every rank
@@ -1023,13 +1146,21 @@ class ShardedCallbacks(object):
     result is ``num_free`` doubles at the most -- and the root adds the
     ranks' shares of the node-invariant tail of ``J^T w`` in rank order.  The
     vectors of the products are created by the first product command.  Block
-    products and the Hessian are not sharded.
+    products are not sharded.
+
+    :meth:`hessian` serves the exact Hessian of the constraint Lagrangian
+    (DESIGN.md section 9.2): ``lagrange`` takes the route ``free`` takes,
+    every rank evaluates its window (:meth:`ShardedCollocator.hessian`) and
+    copies its slice into one shared page-locked vector, which the root
+    returns.  ``hessian_extra``: doubles to keep free behind the constraint
+    section of that vector (``ShardedProblem`` puts the objective's values
+    there).  The vectors of this command are created by its first round.
     """
 
-    _STOP, _CON, _JAC, _BOTH, _JVP, _VJP = 0, 1, 2, 3, 4, 5
+    _STOP, _CON, _JAC, _BOTH, _JVP, _VJP, _HESS = 0, 1, 2, 3, 4, 5, 6
 
     def __init__(self, sharded, name=None, root=0, pin=True,
-                 fresh_constraints=True, jac_host=None):
+                 fresh_constraints=True, jac_host=None, hessian_extra=0):
         import torch
         import torch.distributed as dist
         sh = self.sh = sharded
@@ -1088,6 +1219,9 @@ class ShardedCallbacks(object):
         self._name, self._pin, self._shm = name, pin, shm
         self._pending_vec = self._vec_dev = None
         self.vec_host = self.jv_host = self.jtw_host = self.tails_host = None
+        # the Hessian's vectors: made by the first Hessian command
+        self.hessian_extra = int(hessian_extra)
+        self._lam_dev = self.lam_host = self.hess_host = None
 
     # -- one evaluation, on every rank ------------------------------------------
     def _known_updates(self, free):
@@ -1191,10 +1325,61 @@ class ShardedCallbacks(object):
             torch.cuda.synchronize(sh.device)
         self._dist.barrier(sh.group)            # every slice has landed
 
+    def _hessian_vectors(self):
+        """The vectors of the Hessian command, on every rank in the same round
+        (their creation is collective): the multipliers on the device and,
+        under gloo, in shared host memory; the values -- ``hessian_extra``
+        doubles behind them -- in shared host memory, of which a rank
+        page-locks what it writes (the root: all of it)."""
+        if self.hess_host is not None:
+            return
+        import torch
+        sh = self.sh
+        nnz = sh.hessian_nnz
+        self._lam_dev = torch.empty(sh.num_constraints, dtype=torch.float64,
+                                    device=sh.device)
+        if not self._rccl:
+            self.lam_host = SharedHostVector(
+                self._name + '_lam', sh.num_constraints, sh.rank,
+                pin=self._pin, **self._shm)
+        pin = False
+        if self._pin:
+            pin = True if self.is_root else (
+                sh.a*sh.PH, nnz if sh.rank == sh.tail_rank else sh.b*sh.PH)
+        self.hess_host = SharedHostVector(
+            self._name + '_hess', nnz + self.hessian_extra, sh.rank, pin=pin,
+            **self._shm)
+
+    def _hessian_round(self, flags, params=None, traj=None):
+        import torch
+        sh = self.sh
+        self._hessian_vectors()
+        self._share_known(flags, params, traj)
+        self._load_free()
+        lam = self._lam_dev
+        if self._rccl:
+            if self.is_root:
+                lam.copy_(torch.from_numpy(self._pending_vec))
+            self._dist.broadcast(lam, self.root, group=sh.group)
+        else:
+            # (as the direction of a product: the root fills the shared
+            # vector here, and nobody reads it before the root has)
+            if self.is_root:
+                self.lam_host.array[:] = self._pending_vec
+            self._dist.barrier(sh.group)
+            lam.copy_(self.lam_host.torch_view(), non_blocking=True)
+        sh.hessian(self.free_dev, lam, sync=False)
+        sh.hessian_to_host(self.hess_host)
+        if sh.device.type == 'cuda':
+            torch.cuda.synchronize(sh.device)
+        self._dist.barrier(sh.group)            # every slice has landed
+
     def _round(self, cmd, flags, params=None, traj=None):
         import torch
         if cmd in (self._JVP, self._VJP):
             return self._product_round(cmd, flags, params, traj)
+        if cmd == self._HESS:
+            return self._hessian_round(flags, params, traj)
         what = {self._CON: 'con', self._JAC: 'jac', self._BOTH: 'both'}[cmd]
         self._share_known(flags, params, traj)
         self._load_free()
@@ -1286,6 +1471,17 @@ class ShardedCallbacks(object):
                 parts.reshape(sh.world_size, sh.num_tail))
         return out
 
+    def hessian(self, free, lagrange):
+        """The values of the Hessian of the constraint Lagrangian
+        (``ConstraintCollocator.generate_hessian_function``'s, in its order:
+        node blocks, then the instance entries), every value bit for bit the
+        single-GPU evaluation's.  Returns the persistent shared vector of
+        ``hessian_nnz + hessian_extra`` doubles, which the next call
+        overwrites (as ``jacobian`` does); the constraint section is its
+        first ``hessian_nnz`` entries."""
+        self._call(free, self._HESS, lagrange, 'lagrange')
+        return self.hess_host.array
+
     def shutdown(self):
         """Releases the serving ranks (root only; idempotent)."""
         if self.is_root and self._cmd is not None:
@@ -1308,6 +1504,6 @@ class ShardedCallbacks(object):
         for v in (self.free_host, self.con_host,
                   self.jac_host if self._own_jac_host else None,
                   self.vec_host, self.jv_host, self.jtw_host,
-                  self.tails_host):
+                  self.tails_host, self.lam_host, self.hess_host):
             if v is not None:
                 v.close()
