@@ -180,7 +180,8 @@ typedef struct opty_hip_desc {
  * has them by looking the symbols up; likewise, later still,
  * opty_hip_jacprod_jvp_shard / opty_hip_jacprod_jvp_instance /
  * opty_hip_jacprod_vjp_shard, and then opty_hip_eval_hess_shard /
- * opty_hip_eval_hess_instance / opty_hip_hessian_indices_range), and
+ * opty_hip_eval_hess_instance / opty_hip_hessian_indices_range, and then the
+ * opty_hip_hesscsr_* entry points), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -1010,6 +1011,71 @@ int opty_hip_hessmv_apply_block(opty_hip_hessmv *h, const double *values,
                                 int32_t ncols, int32_t mem);
 /* columns one pass takes (1 .. 4), fixed at create from the LDS the side table needs */
 int32_t opty_hip_hessmv_block_width(const opty_hip_hessmv *h);
+
+/* ---- Hessian as CSR: unique lower triangle, duplicates summed ------------------
+ * The triplets of the Hessian of the Lagrangian -- `values` laid out as for the
+ * Hessian operator above, the descriptor is its descriptor -- compressed to
+ * the CSR lower triangle over num_free rows: exactly the distinct (row, col)
+ * pairs, rows ascending, columns ascending within a row, a row without a
+ * triplet empty; data[u] is the sum of the triplets of pair u.
+ * scipy.sparse.csr_matrix((data, indices, indptr)) needs no conversion.
+ *
+ * The structure depends on the descriptor and N only and is closed form
+ * (hessian_csr_structure of opty_amd/codegen/program.py is the host
+ * statement): trajectory row R*N + p is the merge of the node entries of row
+ * side (R, 0) at node p and of (R, 1) at node p - 1, the same L_R columns at
+ * every interior time node; a tail row is one segment of consecutive time nodes
+ * per trajectory row it couples with, then its tail columns; an explicit
+ * triplet falls on a pair of the pattern or adds a column to its row.
+ *
+ * Kernels (this library's, no code object): `opty_hesscsr` -- lane = time node,
+ * one wave per block, blocks of 64 lanes that advance by 63 nodes; the node
+ * entries of a trajectory row class are a window of consecutive entries, and
+ * the window of a group of consecutive classes (up to 64 entries, or the widest
+ * class's) goes through an LDS tile for the block's 64 nodes; the outputs of a
+ * class leave through a 64 x 33 tile, rows that follow one another in data as
+ * one run; a segment is one coalesced store per lane -- and `opty_hesscsr_fin` -- lane =
+ * item: the first and the last time node of every trajectory row, every row
+ * with an explicit triplet, the tail x tail pairs, each with its list of
+ * positions in `values`; launched when there are items.
+ *
+ * ORDER OF ADDITION.  A SHORT group -- every pair but a tail x tail pair with a
+ * triplet per constraint node -- adds its triplets in ascending position in
+ * `values`, starting from +0.0: the bits of np.add.at(zeros, slot, values).  A
+ * LONG group: per node its triplets in ascending position from +0.0; lanes past
+ * the last node and lane 0 of every block but the first (the repeated node)
+ * count as 0.0; per block the tree x[l] += x[l + d] for d = 32, 16 .. 1; the
+ * block partials in block order from +0.0; then the explicit triplets of the
+ * pair in stored order.  The order depends on N alone: the same bits in every
+ * call and for both memory kinds.  Every element of data is stored exactly
+ * once, without atomics; nothing outside data is written.
+ *
+ * Creation refuses what opty_hip_hessmv_create refuses, a pattern entry above
+ * the diagonal, 2^31 or more triplets, and a pattern in which the node entries
+ * of one row class span so many consecutive entries that the tile (8*(64*(W|1)
+ * + 64*33 + 64) bytes, W = max(64, widest class)) exceeds the LDS of a block,
+ * with the count and the limit in the message.  The handle BORROWS its problem handle (N, n, q, r, s, device,
+ * stream) and must be destroyed before it. */
+typedef struct opty_hip_hesscsr opty_hip_hesscsr;
+
+int opty_hip_hesscsr_create(opty_hip_problem *p,
+                            const opty_hip_hessmv_desc *desc,
+                            opty_hip_hesscsr **out);
+int opty_hip_hesscsr_destroy(opty_hip_hesscsr *h);
+/* input triplets: PH*(N-1) + nnz_inst + E*(N-1) + T */
+int64_t opty_hip_hesscsr_nnz(const opty_hip_hesscsr *h);
+/* distinct (row, col) pairs: the length of indices and of data */
+int64_t opty_hip_hesscsr_nnz_unique(const opty_hip_hesscsr *h);
+/* indptr: num_free + 1, indices: nnz_unique int64 values in `mem` memory;
+ * synchronous for both memory kinds. */
+int opty_hip_hesscsr_structure(opty_hip_hesscsr *h, int64_t *indptr,
+                               int64_t *indices, int32_t mem);
+/* values: hesscsr_nnz doubles (8-byte alignment is enough), data: nnz_unique
+ * doubles, both in `mem` memory.  Synchronous for OPTY_HIP_HOST, enqueued on the
+ * problem's stream for OPTY_HIP_DEVICE.  Refused before anything is enqueued:
+ * null pointers, a data range that overlaps values, a bad memory kind. */
+int opty_hip_hesscsr_compress(opty_hip_hesscsr *h, const double *values,
+                              double *data, int32_t mem);
 
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);

@@ -680,6 +680,295 @@ def assemble_hessmv(N, num_rows, num_tail, values, v, pattern, inst_rows=(),
     return y
 
 
+#: nodes a block of ``opty_hesscsr`` advances by (64 lanes, one repeated node)
+HESSCSR_STRIDE = 63
+
+
+def hesscsr_lds_bytes(width):
+    """LDS of one block of ``opty_hesscsr`` when the widest row class spans
+    ``width`` consecutive node entries (from the first to the last entry whose
+    row side is in the class): the tile of a group of classes -- ``max(64,
+    width)`` entries of the block's 64 nodes at an odd pitch --, the 64 x 33
+    output tile, one row start per lane.  The rule
+    ``opty_hip_hesscsr_create`` applies."""
+    return 8*(64*(max(64, int(width)) | 1) + 64*33 + 64)
+
+
+class _HessianCsrPlan(object):
+    """Where every triplet of the Hessian goes in the CSR lower triangle
+    (:func:`hessian_csr_structure`).  A *source* of an output is a code ``2*e
+    + back``: entry ``e`` of the combined per-node list (node section, then
+    objective section) at node ``p - back``, ``p`` the time node of the
+    output.
+
+    ``runs``: ``(out, p, codes, row, off)`` -- the outputs ``out`` (an index
+    array into ``data``) of the time nodes ``p`` are the sums of the sources
+    ``codes``, their columns are ``row*N + p + off``; ``items``: ``(out,
+    col, positions, long_codes)`` -- one output each, the sum of the values
+    at ``positions`` (ascending) on top of, for a tail x tail pair with
+    per-node sources, the long sum of ``long_codes`` over all nodes."""
+
+    def __init__(self, N, num_rows, num_tail, pattern, inst_rows=(),
+                 inst_cols=(), obj_pattern=(), obj_base=0, tail_rows=(),
+                 tail_cols=()):
+        import numpy as np
+        N = self.N = int(N)
+        ncn = self.ncn = N - 1
+        if ncn < 1:
+            raise ValueError('N %d < 2' % N)
+        num_rows, num_tail = int(num_rows), int(num_tail)
+        sides, _, entries, obj_entries = hessian_side_table(
+            pattern, obj_pattern, obj_base)
+        PH = self.PH = len(entries)
+        E = self.E = len(obj_entries)
+        ni, nt = len(inst_rows), len(tail_rows)
+        self.obj_at = PH*ncn + ni
+        self.nnz = (PH + E)*ncn + ni + nt
+        tail = num_rows*N
+        self.num_free = num_free = tail + num_tail
+
+        # per-node classes: trajectory row R -> {(R', column offset): codes},
+        # tail row j -> {R': codes} (a segment of consecutive time nodes) and
+        # {j': codes} (a long group)
+        traj = [dict() for _ in range(num_rows)]
+        segs = [dict() for _ in range(num_tail)]
+        longs = [dict() for _ in range(num_tail)]
+        for e, (sa, sb) in enumerate(list(entries) + list(obj_entries)):
+            a, b = sides[sa], sides[sb]
+            for row, off in (a, b):
+                if row >= num_rows or (row < 0 and off >= num_tail):
+                    raise ValueError('side (%d, %d) is outside the problem'
+                                     % (row, off))
+            if _side_order(a) < _side_order(b):
+                raise ValueError('entry %d is above the diagonal: %s < %s'
+                                 % (e, a, b))
+            if a[0] >= 0:
+                traj[a[0]].setdefault((b[0], b[1] - a[1]), []).append(
+                    2*e + a[1])
+            elif b[0] >= 0:
+                segs[a[1]].setdefault(b[0], []).append(2*e + b[1])
+            else:
+                longs[a[1]].setdefault(b[1], []).append(2*e)
+
+        def in_order(codes):
+            # ascending position in ``values``: node section, node p - 1
+            # before node p; then the objective section, entry-major
+            return sorted(codes, key=lambda c: (
+                (1, c >> 1, 0) if c >> 1 >= PH else (0, 1 - (c & 1), c >> 1)))
+
+        def valid(codes, p):
+            return [c for c in codes if 0 <= p - (c & 1) < ncn]
+
+        def traj_row(R, p):
+            """{column: positions} of the regular pattern of row (R, p)."""
+            out = {}
+            for (Rp, d), codes in traj[R].items():
+                v = valid(codes, p)
+                if v:
+                    out[Rp*N + p + d] = [int(self.position(c, p)) for c in v]
+            return out
+
+        # explicit triplets: row -> {column: positions in stored order}
+        explicit = {}
+        for rows, cols, at in ((inst_rows, inst_cols, PH*ncn),
+                               (tail_rows, tail_cols, self.obj_at + E*ncn)):
+            for k, (r, c) in enumerate(zip(rows, cols)):
+                r, c = int(r), int(c)
+                if not 0 <= c <= r < num_free:
+                    raise ValueError('explicit entry (%d, %d) is outside the '
+                                     'lower triangle' % (r, c))
+                explicit.setdefault(r, {}).setdefault(c, []).append(at + k)
+
+        # whole rows that the closed form does not cover: the first and last
+        # time node of every trajectory row and rows with explicit triplets
+        whole = {}
+        for R in range(num_rows):
+            for p in (0, ncn):
+                whole[R*N + p] = traj_row(R, p)
+        for r, extra in explicit.items():
+            if r < tail:
+                row = whole.setdefault(r, traj_row(r // N, r % N))
+                for c, at in extra.items():
+                    row.setdefault(c, []).extend(at)
+
+        # tail rows: segments in column order, explicit columns between them
+        tail_rows_ = []
+        for j in range(num_tail):
+            seg = []
+            for Rp in sorted(segs[j]):
+                codes = in_order(segs[j][Rp])
+                lo = 0 if any(c & 1 == 0 for c in codes) else 1
+                hi = ncn if any(c & 1 for c in codes) else ncn - 1
+                seg.append([Rp, lo, hi, codes, {}])
+            extra, tcols = {}, {jp: [] for jp in longs[j]}
+            for c, at in explicit.get(tail + j, {}).items():
+                if c >= tail:
+                    tcols.setdefault(c - tail, []).extend(at)
+                    continue
+                hit = [s for s in seg
+                       if s[0] == c // N and s[1] <= c % N <= s[2]]
+                if hit:
+                    hit[0][4][c % N] = at
+                else:
+                    extra[c] = at
+            tail_rows_.append((seg, extra, tcols))
+
+        lens = np.zeros(num_free, dtype=np.int64)
+        for R in range(num_rows):
+            lens[R*N + 1:R*N + ncn] = len(traj[R])
+        for r, row in whole.items():
+            lens[r] = len(row)
+        for j, (seg, extra, tcols) in enumerate(tail_rows_):
+            lens[tail + j] = sum(s[2] - s[1] + 1 for s in seg) + len(extra) \
+                + len(tcols)
+        indptr = self.indptr = np.concatenate(
+            ([0], np.cumsum(lens))).astype(np.int64)
+        self.nnz_unique = int(indptr[-1])
+
+        runs, items = [], []
+        for R in range(num_rows):
+            p = np.arange(1, ncn, dtype=np.int64)
+            p = p[~np.isin(R*N + p, list(whole))] if len(p) else p
+            start = indptr[R*N + p]
+            for k, key in enumerate(sorted(traj[R])):
+                runs.append((start + k, p, in_order(traj[R][key])) + key)
+        for r, row in whole.items():
+            for k, c in enumerate(sorted(row)):
+                items.append((int(indptr[r]) + k, c, sorted(row[c]), None))
+        for j, (seg, extra, tcols) in enumerate(tail_rows_):
+            at = int(indptr[tail + j])
+            pieces = sorted([(s[0]*N + s[1], s) for s in seg] +
+                            [(c, None) for c in extra], key=lambda t: t[0])
+            for c, s in pieces:
+                if s is None:
+                    items.append((at, c, sorted(extra[c]), None))
+                    at += 1
+                    continue
+                Rp, lo, hi, codes, on = s
+                for a, b in ((0, 0), (1, ncn - 1), (ncn, ncn)):
+                    a, b = max(a, lo), min(b, hi)
+                    if a > b:
+                        continue
+                    p = np.arange(a, b + 1, dtype=np.int64)
+                    p = p[~np.isin(p, list(on))] if on else p
+                    runs.append((at + p - lo, p, valid(codes, a), Rp, 0))
+                for q, more in on.items():
+                    items.append((at + q - lo, Rp*N + q, sorted(
+                        [int(self.position(c, q)) for c in valid(codes, q)]
+                        + more), None))
+                at += hi - lo + 1
+            for jp in sorted(tcols):
+                codes = in_order(longs[j].get(jp, []))
+                items.append((at, tail + jp, list(tcols[jp]), codes or None))
+                at += 1
+            assert at == indptr[tail + j + 1]
+        self.runs, self.items = runs, items
+
+    def position(self, code, p):
+        """Position in ``values`` of source ``code`` of time node(s) ``p``."""
+        e, i = code >> 1, p - (code & 1)
+        if e < self.PH:
+            return i*self.PH + e
+        return self.obj_at + (e - self.PH)*self.ncn + i
+
+    def long_sum(self, values, codes):
+        """The long sum of ``opty_hesscsr`` / ``opty_hesscsr_fin``: per node
+        the sources in order from ``+0.0``; blocks of 64 lanes that advance
+        by 63 nodes, lane 0 of a later block (the repeated node) and lanes
+        past the last node count as ``0.0``; per block the tree ``x[l] +=
+        x[l + d]`` for ``d`` = 32, 16 .. 1; the block partials in block order
+        from ``+0.0``."""
+        import numpy as np
+        ncn = self.ncn
+        node = np.zeros(ncn)
+        i = np.arange(ncn, dtype=np.int64)
+        for c in codes:
+            node = node + values[self.position(c, i)]
+        nblk = (ncn + HESSCSR_STRIDE - 1)//HESSCSR_STRIDE
+        blk, lane = np.arange(nblk)[:, None], np.arange(64)[None, :]
+        at = HESSCSR_STRIDE*blk + lane
+        # (lane 0 of block b > 0 is node 63 b: lane 63 of block b - 1)
+        counts = (at < ncn) & ~((lane == 0) & (blk > 0))
+        x = np.where(counts, node[np.minimum(at, ncn - 1)], 0.0)
+        for d in (32, 16, 8, 4, 2, 1):
+            x[:, :d] = x[:, :d] + x[:, d:2*d]
+        total = 0.0
+        for b in range(nblk):
+            total = total + x[b, 0]
+        return total
+
+
+def hessian_csr_structure(N, num_rows, num_tail, pattern, inst_rows=(),
+                          inst_cols=(), obj_pattern=(), obj_base=0,
+                          tail_rows=(), tail_cols=()):
+    """``(indptr, indices, slot)`` (int64) of the Hessian's lower triangle in
+    compressed-sparse-row form over ``num_rows*N + num_tail`` rows: exactly
+    the distinct ``(row, col)`` pairs of the triplets ``[node section (i*PH +
+    e) | instance entries | objective section (e*(N-1) + j) | parameter-
+    parameter entries]`` (the arguments are :func:`assemble_hessmv`'s), rows
+    ascending, columns ascending within a row; ``slot[k]`` is the position in
+    ``data`` of triplet ``k``.
+
+    Closed form, nothing is sorted over the triplets: a node's entries of row
+    side ``(R, 0)`` and those of ``(R, 1)`` at the node before are two runs in
+    ascending column order (:func:`build_hessian_program`), so row ``R*N + p``
+    is their merge -- ``len(class)`` columns at every interior time node, a
+    sub-list at the first and the last --; a tail row is one segment of
+    consecutive time nodes per trajectory row it couples with, then its tail
+    columns.  Explicit triplets (instance, parameter-parameter) fall on a
+    pair of the pattern or add a column to their row."""
+    import numpy as np
+    plan = _HessianCsrPlan(N, num_rows, num_tail, pattern, inst_rows,
+                           inst_cols, obj_pattern, obj_base, tail_rows,
+                           tail_cols)
+    indices = np.full(plan.nnz_unique, -1, dtype=np.int64)
+    slot = np.full(plan.nnz, -1, dtype=np.int64)
+    every = np.arange(plan.ncn, dtype=np.int64)
+    for out, p, codes, row, off in plan.runs:
+        indices[out] = row*plan.N + p + off
+        for c in codes:
+            slot[plan.position(c, p)] = out
+    for out, col, at, long_codes in plan.items:
+        indices[out] = col
+        if at:
+            slot[at] = out
+        for c in long_codes or ():
+            slot[plan.position(c, every)] = out
+    assert np.all(indices >= 0) and np.all(slot >= 0)
+    return plan.indptr, indices, slot
+
+
+def assemble_hessian_csr(N, num_rows, num_tail, values, pattern,
+                         inst_rows=(), inst_cols=(), obj_pattern=(),
+                         obj_base=0, tail_rows=(), tail_cols=()):
+    """``data`` of the CSR lower triangle of :func:`hessian_csr_structure`
+    from the triplets ``values``: element ``u`` is the sum of the triplets of
+    pair ``u``.  The host statement of ``opty_hesscsr`` / ``opty_hesscsr_fin``:
+    a short group adds its triplets in ascending position in ``values`` from
+    ``+0.0`` (the bits of ``np.add.at``); a long group -- a tail x tail pair
+    with a triplet per constraint node -- adds the block partials of
+    :meth:`_HessianCsrPlan.long_sum` in block order, then its explicit
+    triplets in stored order."""
+    import numpy as np
+    plan = _HessianCsrPlan(N, num_rows, num_tail, pattern, inst_rows,
+                           inst_cols, obj_pattern, obj_base, tail_rows,
+                           tail_cols)
+    values = np.asarray(values, dtype=float)
+    assert values.shape == (plan.nnz,)
+    data = np.zeros(plan.nnz_unique)
+    for out, p, codes, _, _ in plan.runs:
+        x = np.zeros(len(p))
+        for c in codes:
+            x = x + values[plan.position(c, p)]
+        data[out] = x
+    for out, _, at, long_codes in plan.items:
+        x = plan.long_sum(values, long_codes) if long_codes else 0.0
+        for k in at:
+            x = x + values[k]
+        data[out] = x
+    return data
+
+
 def matrix_program(dag, outputs, num_vec, num_const, shape):
     """Program of a plain matrix of expressions (the reference's
     ``ufuncify_matrix`` call shape, ``opty/utils.py:639-640``): ``outputs`` are

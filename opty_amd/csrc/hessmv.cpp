@@ -369,48 +369,6 @@ struct opty_hip_hessmv : Borrowed {
 
 namespace {
 
-int check_pattern(const char *what, const int32_t *pat, int count, int base,
-                  int nrows, int ntail) {
-    for (int e = 0; e < count; ++e)
-        for (int k = 0; k < 2; ++k) {
-            const int row = pat[4*e + 2*k], off = pat[4*e + 2*k + 1];
-            if (row < -1 || row >= nrows)
-                return fail("%s entry %d: row %d outside [-1, %d)", what, e,
-                            row, nrows);
-            if (row >= 0 && (base + off < 0 || base + off > 1))
-                return fail("%s entry %d: slot %d outside {0, 1}", what, e,
-                            base + off);
-            if (row < 0 && (off < 0 || off >= ntail))
-                return fail("%s entry %d: tail offset %d outside [0, %d)",
-                            what, e, off, ntail);
-        }
-    return 0;
-}
-
-int check_explicit(const char *what, const int64_t *rows, const int64_t *cols,
-                   int count, int64_t num_free) {
-    for (int k = 0; k < count; ++k) {
-        if (rows[k] < 0 || rows[k] >= num_free || cols[k] < 0 ||
-            cols[k] >= num_free)
-            return fail("%s entry %d: (%lld, %lld) outside [0, %lld)", what,
-                        k, (long long)rows[k], (long long)cols[k],
-                        (long long)num_free);
-        if (rows[k] < cols[k])
-            return fail("%s entry %d: (%lld, %lld) is above the diagonal "
-                        "(row < col)", what, k, (long long)rows[k],
-                        (long long)cols[k]);
-    }
-    return 0;
-}
-
-template <typename T>
-int upload(T **dev, const T *host, size_t count) {
-    if (!count) return 0;
-    HIP_TRY(hipMalloc((void **)dev, count*sizeof(T)));
-    HIP_TRY(hipMemcpy(*dev, host, count*sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 // A staging vector of at least `count` values (a larger request replaces it:
 // the host calls that use it have returned, so nothing reads it any more).
 int grow(double **ptr, size_t *cap, size_t count) {
@@ -526,32 +484,8 @@ int opty_hip_hessmv_create(opty_hip_problem *p,
                            const opty_hip_hessmv_desc *desc,
                            opty_hip_hessmv **out) {
     if (!p || !desc || !out) return fail("null argument");
-    if (desc->PH < 0 || desc->nnz_inst < 0 || desc->E < 0 || desc->T < 0)
-        return fail("bad Hessian-product descriptor (PH %d, nnz_inst %d, E "
-                    "%d, T %d)", desc->PH, desc->nnz_inst, desc->E, desc->T);
-    if (desc->PH > 0 && !desc->pattern) return fail("null index pattern");
-    if (desc->E > 0 && !desc->obj_pattern)
-        return fail("null objective index pattern");
-    if (desc->nnz_inst > 0 && (!desc->inst_rows || !desc->inst_cols))
-        return fail("null instance indices");
-    if (desc->T > 0 && (!desc->tail_rows || !desc->tail_cols))
-        return fail("null parameter-parameter indices");
-    if (desc->E > 0 && desc->obj_base != 0 && desc->obj_base != 1)
-        return fail("obj_base %d outside {0, 1}", desc->obj_base);
-    if (p->d.N < 2) return fail("N %lld < 2", (long long)p->d.N);
+    if (int rc = check_hessmv_desc(p, desc)) return rc;
     const int nrows = p->d.n + p->d.q, ntail = p->d.r + p->d.s;
-    if (int rc = check_pattern("pattern", desc->pattern, desc->PH, 0, nrows,
-                               ntail))
-        return rc;
-    if (int rc = check_pattern("objective pattern", desc->obj_pattern,
-                               desc->E, desc->obj_base, nrows, ntail))
-        return rc;
-    if (int rc = check_explicit("instance", desc->inst_rows, desc->inst_cols,
-                                desc->nnz_inst, p->num_free()))
-        return rc;
-    if (int rc = check_explicit("parameter-parameter", desc->tail_rows,
-                                desc->tail_cols, desc->T, p->num_free()))
-        return rc;
 
     // the side table: distinct (row, slot) in ascending order, then the tail
     // offsets in ascending order (hessian_side_table of codegen/program.py)

@@ -14,6 +14,8 @@
 //   jacprod.cpp       the Jacobian-product handle (J v, J^T w; borrows too)
 //   hessmv.cpp        the Hessian-product handle (H v from the stored
 //                     triplets; borrows too, kernels of its own)
+//   hesscsr.cpp       the CSR-Hessian handle (the triplets compressed to the
+//                     unique lower triangle; borrows too, kernels of its own)
 //   referee.cpp       (libopty_hip_referee.so) instruction-tape kernel and
 //                     register poisoner of the build verification
 #pragma once
@@ -349,6 +351,82 @@ inline void borrowed_destroy(Borrowed *b, std::initializer_list<void *> bufs) {
     for (void *buf : bufs)
         if (buf) (void)hipFree(buf);
     if (b->module) (void)hipModuleUnload(b->module);
+}
+
+// ---------------------------------------------------------------------------
+// What the handles over the Hessian's triplets share (hessmv.cpp,
+// hesscsr.cpp): the checks of an opty_hip_hessmv_desc and the upload of a
+// host table.
+inline int check_pattern(const char *what, const int32_t *pat, int count,
+                         int base, int nrows, int ntail) {
+    for (int e = 0; e < count; ++e)
+        for (int k = 0; k < 2; ++k) {
+            const int row = pat[4*e + 2*k], off = pat[4*e + 2*k + 1];
+            if (row < -1 || row >= nrows)
+                return fail("%s entry %d: row %d outside [-1, %d)", what, e,
+                            row, nrows);
+            if (row >= 0 && (base + off < 0 || base + off > 1))
+                return fail("%s entry %d: slot %d outside {0, 1}", what, e,
+                            base + off);
+            if (row < 0 && (off < 0 || off >= ntail))
+                return fail("%s entry %d: tail offset %d outside [0, %d)",
+                            what, e, off, ntail);
+        }
+    return 0;
+}
+
+inline int check_explicit(const char *what, const int64_t *rows,
+                          const int64_t *cols, int count, int64_t num_free) {
+    for (int k = 0; k < count; ++k) {
+        if (rows[k] < 0 || rows[k] >= num_free || cols[k] < 0 ||
+            cols[k] >= num_free)
+            return fail("%s entry %d: (%lld, %lld) outside [0, %lld)", what,
+                        k, (long long)rows[k], (long long)cols[k],
+                        (long long)num_free);
+        if (rows[k] < cols[k])
+            return fail("%s entry %d: (%lld, %lld) is above the diagonal "
+                        "(row < col)", what, k, (long long)rows[k],
+                        (long long)cols[k]);
+    }
+    return 0;
+}
+
+// Everything opty_hip_hessmv_create refuses in a descriptor.
+inline int check_hessmv_desc(const opty_hip_problem *p,
+                             const opty_hip_hessmv_desc *desc) {
+    if (desc->PH < 0 || desc->nnz_inst < 0 || desc->E < 0 || desc->T < 0)
+        return fail("bad Hessian-product descriptor (PH %d, nnz_inst %d, E "
+                    "%d, T %d)", desc->PH, desc->nnz_inst, desc->E, desc->T);
+    if (desc->PH > 0 && !desc->pattern) return fail("null index pattern");
+    if (desc->E > 0 && !desc->obj_pattern)
+        return fail("null objective index pattern");
+    if (desc->nnz_inst > 0 && (!desc->inst_rows || !desc->inst_cols))
+        return fail("null instance indices");
+    if (desc->T > 0 && (!desc->tail_rows || !desc->tail_cols))
+        return fail("null parameter-parameter indices");
+    if (desc->E > 0 && desc->obj_base != 0 && desc->obj_base != 1)
+        return fail("obj_base %d outside {0, 1}", desc->obj_base);
+    if (p->d.N < 2) return fail("N %lld < 2", (long long)p->d.N);
+    const int nrows = p->d.n + p->d.q, ntail = p->d.r + p->d.s;
+    if (int rc = check_pattern("pattern", desc->pattern, desc->PH, 0, nrows,
+                               ntail))
+        return rc;
+    if (int rc = check_pattern("objective pattern", desc->obj_pattern,
+                               desc->E, desc->obj_base, nrows, ntail))
+        return rc;
+    if (int rc = check_explicit("instance", desc->inst_rows, desc->inst_cols,
+                                desc->nnz_inst, p->num_free()))
+        return rc;
+    return check_explicit("parameter-parameter", desc->tail_rows,
+                          desc->tail_cols, desc->T, p->num_free());
+}
+
+template <typename T>
+int upload(T **dev, const T *host, size_t count) {
+    if (!count) return 0;
+    HIP_TRY(hipMalloc((void **)dev, count*sizeof(T)));
+    HIP_TRY(hipMemcpy(*dev, host, count*sizeof(T), hipMemcpyHostToDevice));
+    return 0;
 }
 
 }  // namespace opty

@@ -1732,6 +1732,141 @@ class ConstraintCollocator(object):
         # function's persistent buffer and is copied to the device)
         return self._hessian_operator(self._ensure_hessmv(), values)
 
+    # ------------------------------------------------------------------
+    # Hessian as CSR: unique lower triangle
+    # ------------------------------------------------------------------
+    def _ensure_hesscsr(self, objective=None):
+        """The CSR-Hessian handle (made on first use; one for the constraint
+        triplets alone, one per objective Hessian handle)."""
+        attr = '_hesscsr' if objective is None else '_hesscsr_objective'
+        if objective is not None and \
+                getattr(self, '_hesscsr_objective_of', None) is not objective:
+            old = getattr(self, attr, None)
+            if old is not None:
+                old.release()
+            setattr(self, attr, None)
+            self._hesscsr_objective_of = objective
+
+        def create(hip):
+            return hb.HipHessianCsr(
+                hip, self._hessmv_descriptor(objective)), {}
+        # (no program of its own: the compression is checked against
+        # scipy.sparse on the triplets by the test suite)
+        return self._ensure_derived(attr, create, lambda handle: None)
+
+    @staticmethod
+    def _hessian_csr_structure_of(handle):
+        """``(indptr, indices)`` (int64) from ``handle``'s closed form."""
+        indptr = np.empty(handle._problem.num_free + 1, dtype=np.int64)
+        indices = np.empty(handle.nnz_unique, dtype=np.int64)
+        handle.structure(indptr, indices, hb.HOST)
+        return indptr, indices
+
+    def hessian_csr_structure(self):
+        """``(indptr, indices)`` (int64, as :meth:`jacobian_csr_structure`)
+        of the constraint part of the Hessian of the Lagrangian in
+        compressed-sparse-row form: the lower triangle over ``num_free``
+        rows, exactly the distinct ``(row, col)`` pairs of
+        :meth:`hessian_indices`, rows ascending, columns ascending within a
+        row.  The values of :meth:`generate_hessian_csr_function` are ``data``
+        of ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(num_free,
+        num_free))`` as they are (``has_canonical_format``)."""
+        # (what has no Hessian is refused before a device is asked for)
+        self._build_hessian_program()
+        self._ensure_hessian()
+        return self._hessian_csr_structure_of(self._ensure_hesscsr())
+
+    def _hessian_csr_compress(self, handle):
+        """``compress(values) -> data`` over ``handle``: host triplets in, a
+        persistent page-locked array out; a torch CUDA tensor in, a new CUDA
+        tensor out."""
+        hip = self._hip
+        nnz, nu = handle.nnz, handle.nnz_unique
+        result = hb.pinned_empty(nu)
+
+        def compress(values):
+            if hasattr(values, 'data_ptr'):
+                import torch
+                if tuple(values.shape) != (nnz,):
+                    raise ValueError('values have the wrong shape')
+                values = values.to(torch.float64).contiguous()
+                out = torch.empty(nu, dtype=torch.float64,
+                                  device=values.device)
+                torch.cuda.current_stream(values.device).synchronize()
+                handle.compress(values, out, hb.DEVICE)
+                hip.synchronize()
+                return out
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            if values.shape != (nnz,):
+                raise ValueError('values must have shape ({},), got {}'
+                                 .format(nnz, values.shape))
+            handle.compress(values, result, hb.HOST)
+            return result
+        compress.result = result
+        return compress
+
+    def generate_hessian_csr_function(self):
+        """Returns ``hcsr(free, lagrange) -> ndarray (nnz_unique,)``: the
+        constraint part of the Hessian of the Lagrangian as ``data`` of the
+        CSR lower triangle of :meth:`hessian_csr_structure`, every pair
+        once.  The triplets of :meth:`generate_hessian_function` are
+        evaluated into a device buffer that the function owns and compressed
+        on the GPU; the triplets of a pair are added in a fixed order (a pair
+        with up to a few triplets: ascending position, the bits of
+        ``np.add.at``), every element is stored exactly once: the same inputs
+        give the same bits.  The result is a persistent page-locked buffer
+        that the next call overwrites.
+
+        ``free`` and ``lagrange`` may also be torch CUDA tensors; the result
+        is then a new CUDA tensor (nothing crosses PCIe).  ``hcsr.compress(
+        values)`` does the same for triplets the caller already holds."""
+        self._build_hessian_program()
+        hess = self._ensure_hessian()
+        handle = self._ensure_hesscsr()
+        hip = self._hip
+        nfree, ncon = self.num_free, self.num_constraints
+        compress = self._hessian_csr_compress(handle)
+        own = {}
+
+        def evaluate(free, lagrange):
+            if hasattr(free, 'data_ptr'):
+                import torch
+                if tuple(free.shape) != (nfree,) or \
+                        tuple(lagrange.shape) != (ncon,):
+                    raise ValueError('free / lagrange have the wrong shape')
+                free = free.to(torch.float64).contiguous()
+                lagrange = lagrange.to(device=free.device,
+                                       dtype=torch.float64).contiguous()
+                self._sync_known(hip, free.cpu().numpy()
+                                 if self._callable_known else None)
+                values = own.get('torch')
+                if values is None or values.device != free.device:
+                    values = own['torch'] = torch.empty(
+                        hess.nnz, dtype=torch.float64, device=free.device)
+                torch.cuda.current_stream(free.device).synchronize()
+                hess.evaluate(free, lagrange, values, hb.DEVICE)
+                return compress(values)
+            free = self._host_free(free)
+            lagrange = np.ascontiguousarray(lagrange, dtype=np.float64)
+            if lagrange.shape != (ncon,):
+                raise ValueError('lagrange must have shape ({},), got {}'
+                                 .format(ncon, lagrange.shape))
+            self._sync_known(hip, free)
+            if 'host' not in own:
+                own['host'] = tuple(
+                    hb.DeviceVector(np.zeros(k), self._device)
+                    for k in (nfree, ncon, hess.nnz, handle.nnz_unique))
+            d_free, d_lam, d_values, d_data = own['host']
+            d_free.assign(free)
+            d_lam.assign(lagrange)
+            hess.evaluate(d_free, d_lam, d_values, hb.DEVICE)
+            handle.compress(d_values, d_data, hb.DEVICE)
+            hip.synchronize()
+            return d_data.read_into(compress.result)
+        evaluate.handle = handle
+        evaluate.compress = compress
+        return evaluate
+
     def generate_source(self):
         """HIP source of this problem's kernels and its launch metadata."""
         return self._emit(self._printer_options())
@@ -3502,21 +3637,14 @@ class Problem(object):
         self.hessianstructure = hessianstructure
         self.hessian = hessian
 
-        def hessian_operator(free, lagrange, obj_factor=1.0):
-            """The Hessian of the Lagrangian at ``(free, lagrange,
-            obj_factor)`` -- constraint triplets, then the objective's -- as
-            a ``scipy.sparse.linalg.LinearOperator`` of shape ``(num_free,
-            num_free)`` (:meth:`ConstraintCollocator.hessian_operator`): the
-            triplets are evaluated once into a device buffer that the
-            operator owns (``.values``), every product runs on the GPU.
-            Needs a device-backed ``obj_hessian``
-            (``opty_amd.create_objective_hessian_function``)."""
+        def objective_handle(method):
+            """The device handle of ``values``, of this problem's sizes."""
             if not on_device:
                 raise TypeError(
-                    'Problem.hessian_operator needs an obj_hessian whose '
+                    'Problem.%s needs an obj_hessian whose '
                     'values have a device handle (values.handle: opty_amd.'
                     'create_objective_hessian_function); a hand-written '
-                    'values callable has no index pattern to fuse.')
+                    'values callable has no index pattern to fuse.' % method)
             objective = values.handle
             prog = col._build_hessian_program()
             want = dict(N=col.num_collocation_nodes, n=prog.n, q=prog.q,
@@ -3526,6 +3654,18 @@ class Problem(object):
                 raise ValueError(
                     'the objective Hessian was built for %s, the problem '
                     'has %s' % (have, dict(want, s=prog.s)))
+            return objective
+
+        def hessian_operator(free, lagrange, obj_factor=1.0):
+            """The Hessian of the Lagrangian at ``(free, lagrange,
+            obj_factor)`` -- constraint triplets, then the objective's -- as
+            a ``scipy.sparse.linalg.LinearOperator`` of shape ``(num_free,
+            num_free)`` (:meth:`ConstraintCollocator.hessian_operator`): the
+            triplets are evaluated once into a device buffer that the
+            operator owns (``.values``), every product runs on the GPU.
+            Needs a device-backed ``obj_hessian``
+            (``opty_amd.create_objective_hessian_function``)."""
+            objective = objective_handle('hessian_operator')
             handle = col._ensure_hessmv(objective)
             if hasattr(free, 'data_ptr'):
                 vals = hessian(free, lagrange, obj_factor)
@@ -3534,6 +3674,36 @@ class Problem(object):
                                lagrange, obj_factor)
             return col._hessian_operator(handle, vals)
         self.hessian_operator = hessian_operator
+
+        def hessian_csr_structure():
+            """``(indptr, indices)`` (int64) of the Hessian of the
+            Lagrangian -- the ``[constraint | objective]`` triplets of
+            ``hessianstructure()`` -- as the CSR lower triangle over
+            ``num_free`` rows, every pair once, rows and columns ascending
+            (:meth:`ConstraintCollocator.hessian_csr_structure`).  Needs a
+            device-backed ``obj_hessian``."""
+            handle = col._ensure_hesscsr(
+                objective_handle('hessian_csr_structure'))
+            return col._hessian_csr_structure_of(handle)
+
+        csr = {}
+
+        def hessian_csr(free, lagrange, obj_factor=1.0):
+            """``data`` of ``hessian_csr_structure()`` at ``(free, lagrange,
+            obj_factor)``: the triplets of ``hessian(...)`` compressed on the
+            GPU, the triplets of a pair summed in a fixed order
+            (:meth:`ConstraintCollocator.generate_hessian_csr_function`).
+            Host arrays in: a persistent page-locked array out; torch CUDA
+            tensors in: a new CUDA tensor out."""
+            handle = col._ensure_hesscsr(objective_handle('hessian_csr'))
+            if csr.get('handle') is not handle:
+                csr.update(handle=handle,
+                           compress=col._hessian_csr_compress(handle))
+            if not hasattr(free, 'data_ptr'):
+                free = np.ascontiguousarray(free, dtype=float)
+            return csr['compress'](hessian(free, lagrange, obj_factor))
+        self.hessian_csr_structure = hessian_csr_structure
+        self.hessian_csr = hessian_csr
 
     bounds = property(lambda self: self._bounds)
     eom_bounds = property(lambda self: self._eom_bounds)
@@ -3791,6 +3961,15 @@ class ShardedProblem(Problem):
     def hessian_operator(self, free, lagrange, obj_factor=1.0):
         raise NotImplementedError('the Hessian is not sharded: '
                                   'ShardedProblem has no hessian_operator.')
+
+    def hessian_csr_structure(self):
+        raise NotImplementedError(
+            'the Hessian is not sharded: ShardedProblem has no '
+            'hessian_csr_structure.')
+
+    def hessian_csr(self, free, lagrange, obj_factor=1.0):
+        raise NotImplementedError('the Hessian is not sharded: '
+                                  'ShardedProblem has no hessian_csr.')
 
     def _install_hessian(self, obj_hessian):
         """``hessianstructure()`` and ``hessian(free, lagrange,

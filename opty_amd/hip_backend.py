@@ -75,7 +75,8 @@ def _hipcc():
 #: translation units of libopty_hip.so (csrc/opty_internal.h says what is
 #: where) and of the build referee's own library
 RUNTIME_SOURCES = ('runtime.cpp', 'programs.cpp', 'host_scatter.cpp',
-                   'comm.cpp', 'hessian.cpp', 'jacprod.cpp', 'hessmv.cpp')
+                   'comm.cpp', 'hessian.cpp', 'jacprod.cpp', 'hessmv.cpp',
+                   'hesscsr.cpp')
 REFEREE_SOURCES = ('referee.cpp',)
 REFEREE_PATH = os.path.join(_PKG, 'libopty_hip_referee.so')
 
@@ -600,6 +601,16 @@ _SIGNATURES = {
                                      ctypes.c_int64, ctypes.c_int32,
                                      ctypes.c_int32]),
     'opty_hip_hessmv_block_width': (ctypes.c_int32, [_P]),
+    'opty_hip_hesscsr_create': (ctypes.c_int,
+                                [_P, ctypes.POINTER(_HessmvDesc),
+                                 ctypes.POINTER(_P)]),
+    'opty_hip_hesscsr_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_hesscsr_nnz': (ctypes.c_int64, [_P]),
+    'opty_hip_hesscsr_nnz_unique': (ctypes.c_int64, [_P]),
+    'opty_hip_hesscsr_structure': (ctypes.c_int, [_P, _P, _P,
+                                                  ctypes.c_int32]),
+    'opty_hip_hesscsr_compress': (ctypes.c_int, [_P, _P, _P,
+                                                 ctypes.c_int32]),
     'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
                                                 ctypes.c_int64]),
     'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
@@ -750,12 +761,17 @@ class DeviceVector(object):
             _check(self._lib.opty_hip_memcpy(self.ptr, host.ctypes.data,
                                              host.nbytes, 0))
 
-    def numpy(self):
-        out = np.empty(self.size)
+    def read_into(self, out):
+        """Copies the vector into the contiguous float64 host array
+        ``out`` of ``size`` values."""
+        assert out.size == self.size and out.dtype == np.float64
         if self.size:
             _check(self._lib.opty_hip_memcpy(out.ctypes.data, self.ptr,
                                              out.nbytes, 1))
         return out
+
+    def numpy(self):
+        return self.read_into(np.empty(self.size))
 
     def close(self):
         if self.ptr:
@@ -1499,16 +1515,15 @@ class HipJacobianBlockProduct(_DerivedHandle):
             mem))
 
 
-class HipHessianProduct(_DerivedHandle):
-    """One ``opty_hip_hessmv`` handle: ``y = H v`` from the stored triplets of
-    the Hessian of the Lagrangian of a :class:`HipProblem`, which it borrows
-    for its sizes, device and stream (no code object: the kernels are the
-    runtime library's).  ``desc``: ``PH, pattern, inst_rows, inst_cols`` and,
-    with an objective section, ``E, obj_pattern, obj_base, tail_rows,
-    tail_cols`` (``include/opty_hip.h``).  Released and created again with
-    the problem's C handle, as the other derived handles are."""
-
-    _create, _destroy = 'opty_hip_hessmv_create', 'opty_hip_hessmv_destroy'
+class _HessianTripletsHandle(_DerivedHandle):
+    """A handle over the stored triplets of the Hessian of the Lagrangian,
+    made from an ``opty_hip_hessmv_desc``: ``desc`` holds ``PH, pattern,
+    inst_rows, inst_cols`` and, with an objective section, ``E, obj_pattern,
+    obj_base, tail_rows, tail_cols`` (``include/opty_hip.h``).  It borrows
+    its :class:`HipProblem` for sizes, device and stream (no code object: the
+    kernels are the runtime library's) and is released and created again
+    with the problem's C handle, as the other derived handles are.
+    Subclasses name ``_nnz``, the symbol that counts the triplets."""
 
     def __init__(self, problem, desc):
         def table(key, dtype, width):
@@ -1527,7 +1542,7 @@ class HipHessianProduct(_DerivedHandle):
             obj_base=desc.get('obj_base', 0),
             T=desc.get('T', len(self._trows)))
         super().__init__(problem, None)
-        self.nnz = self._lib.opty_hip_hessmv_nnz(self._h)
+        self.nnz = getattr(self._lib, self._nnz)(self._h)
 
     def _descriptor(self):
         def ptr(a):
@@ -1537,6 +1552,15 @@ class HipHessianProduct(_DerivedHandle):
             inst_cols=ptr(self._icols), obj_pattern=ptr(self._obj_pattern),
             tail_rows=ptr(self._trows), tail_cols=ptr(self._tcols),
             **{k: int(v) for k, v in self._counts.items()})
+
+
+class HipHessianProduct(_HessianTripletsHandle):
+    """One ``opty_hip_hessmv`` handle: ``y = H v`` from the stored triplets of
+    the Hessian of the Lagrangian of a :class:`HipProblem`
+    (:class:`_HessianTripletsHandle`)."""
+
+    _create, _destroy = 'opty_hip_hessmv_create', 'opty_hip_hessmv_destroy'
+    _nnz = 'opty_hip_hessmv_nnz'
 
     def sides(self):
         """``(sides, number of trajectory sides)`` of the handle's side
@@ -1567,3 +1591,27 @@ class HipHessianProduct(_DerivedHandle):
         _check(self._lib.opty_hip_hessmv_apply_block(
             self._handle(), _ptr(values), _ptr(V), int(ldv), _ptr(Y),
             int(ldy), int(ncols), mem))
+
+
+class HipHessianCsr(_HessianTripletsHandle):
+    """One ``opty_hip_hesscsr`` handle: the stored triplets of the Hessian of
+    the Lagrangian of a :class:`HipProblem` compressed to the CSR lower
+    triangle, every pair once, duplicates summed in a fixed order
+    (:class:`_HessianTripletsHandle`; ``include/opty_hip.h``, "Hessian as
+    CSR")."""
+
+    _create, _destroy = 'opty_hip_hesscsr_create', 'opty_hip_hesscsr_destroy'
+    _nnz = 'opty_hip_hesscsr_nnz'
+
+    @property
+    def nnz_unique(self):
+        """Distinct ``(row, col)`` pairs: the length of ``data``."""
+        return int(self._lib.opty_hip_hesscsr_nnz_unique(self._handle()))
+
+    def structure(self, indptr, indices, mem):
+        _check(self._lib.opty_hip_hesscsr_structure(
+            self._handle(), _ptr(indptr), _ptr(indices), mem))
+
+    def compress(self, values, data, mem):
+        _check(self._lib.opty_hip_hesscsr_compress(
+            self._handle(), _ptr(values), _ptr(data), mem))
