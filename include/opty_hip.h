@@ -181,7 +181,9 @@ typedef struct opty_hip_desc {
  * opty_hip_jacprod_jvp_shard / opty_hip_jacprod_jvp_instance /
  * opty_hip_jacprod_vjp_shard, and then opty_hip_eval_hess_shard /
  * opty_hip_eval_hess_instance / opty_hip_hessian_indices_range, and then the
- * opty_hip_hesscsr_* entry points), and
+ * opty_hip_hesscsr_* entry points, and then
+ * opty_hip_hesscsr_create_with_diagonal and the opty_hip_kktcsr_* entry
+ * points), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -1076,6 +1078,102 @@ int opty_hip_hesscsr_structure(opty_hip_hesscsr *h, int64_t *indptr,
  * null pointers, a data range that overlaps values, a bad memory kind. */
 int opty_hip_hesscsr_compress(opty_hip_hesscsr *h, const double *values,
                               double *data, int32_t mem);
+
+/* The same handle with EVERY diagonal pair stored, last in its row, whether or
+ * not a triplet lands on it: an empty source list for (R, 0) in every
+ * trajectory row class, in every whole row that items own and in every tail
+ * row; a pair without a triplet is stored as +0.0 by the same kernels.
+ * Everything else (arguments, refusals, the other entry points, the order of
+ * addition) is opty_hip_hesscsr_create's. */
+int opty_hip_hesscsr_create_with_diagonal(opty_hip_problem *p,
+                                          const opty_hip_hessmv_desc *desc,
+                                          opty_hip_hesscsr **out);
+
+/* ---- Augmented system as CSR ---------------------------------------------------
+ * The lower triangle of the interior-point augmented system
+ *
+ *     K = [[ W + diag(sigma) + delta_w I ,  J^T        ],
+ *          [ J                           ,  -delta_c I ]]
+ *     W = obj_factor d2f + sum_k lagrange_k d2c_k
+ *
+ * over n + m rows (n = num_free, m = num_constraints) as one CSR matrix with
+ * int64 indptr (n + m + 1 entries) and indices: rows and columns ascend, every
+ * pair is stored once (scipy: has_canonical_format), EVERY diagonal is stored
+ * and is the last entry of its row -- delta_w and delta_c change between two
+ * factorisations without a new structure.  The structure depends on the
+ * descriptor, the block pattern, the instance indices and N only
+ * (kkt_csr_structure of opty_amd/codegen/program.py is the host statement).
+ *
+ *   row r < n:  the columns of row r of the CSR Hessian above, and the
+ *       diagonal (r, r) whether or not a triplet lands on it.
+ *   row n + k:  the columns of row k of the CSR Jacobian (OPTY_HIP_LAYOUT_CSR:
+ *       rows j*(N-1) + i, then the instance constraints), then the diagonal
+ *       (n + k, n + k).  Row (j, i) holds L_j + 1 values and starts at
+ *       nnz_hessian + (S_j + j)*(N-1) + i*(L_j + 1).
+ *
+ * Values.  An off-diagonal entry of the W block has the bits of the matching
+ * element of opty_hip_hesscsr_compress (the same order of addition).  A
+ * diagonal of the W block is (h + sigma_r) + delta_w, rounded in that order,
+ * h the compressed element or +0.0 where no triplet lands, sigma_r +0.0
+ * when sigma is NULL.  A Jacobian entry has the bits of jac_values at its
+ * position.  A diagonal of the constraint block is 0.0 - delta_c.  Every
+ * element of data is stored exactly once (a W diagonal by the compression,
+ * then updated in place), without atomics; nothing outside data and the
+ * handle's staging buffers is written; the same inputs give the same bits in
+ * every call and for both memory kinds.
+ *
+ * Kernels (this library's): opty_hesscsr / opty_hesscsr_fin write the W part
+ * straight into data[0 .. nnz_hessian); `opty_kkt_diag` -- lane = free row, one
+ * index read per row --, `opty_kkt_jrows` -- the destination spans of the
+ * equations swept flat in tiles of 2048 doubles, 16-byte stores counted from a
+ * 16-byte boundary, one launch with a capped grid -- and `opty_kkt_inst` -- lane
+ * = stored value of the instance rows -- follow on the problem's stream.
+ *
+ * Creation refuses, before a device is touched, a problem handle whose layout
+ * is not OPTY_HIP_LAYOUT_CSR, a block pattern or instance indices that were
+ * never set, columns of an equation that do not ascend and an instance tail
+ * that is not sorted by row, then column; then what
+ * opty_hip_hesscsr_create refuses.  All positions are 64-bit: only the
+ * Hessian's triplets are held to fewer than 2^31.  Before anything is
+ * uploaded, every span is checked to stay inside data.  The handle BORROWS its
+ * problem handle and must be destroyed before it. */
+typedef struct opty_hip_kktcsr opty_hip_kktcsr;
+
+int opty_hip_kktcsr_create(opty_hip_problem *p,
+                           const opty_hip_hessmv_desc *desc,
+                           opty_hip_kktcsr **out);
+int opty_hip_kktcsr_destroy(opty_hip_kktcsr *h);
+/* stored values of K: the length of indices and of data */
+int64_t opty_hip_kktcsr_nnz(const opty_hip_kktcsr *h);
+/* stored values of the W block (diagonals included): data[0 .. nnz_hessian) */
+int64_t opty_hip_kktcsr_nnz_hessian(const opty_hip_kktcsr *h);
+/* the Hessian's triplets: the length of hess_values */
+int64_t opty_hip_kktcsr_nnz_triplets(const opty_hip_kktcsr *h);
+/* indptr: n + m + 1, indices: kktcsr_nnz int64 values in `mem` memory;
+ * synchronous for both memory kinds. */
+int opty_hip_kktcsr_structure(opty_hip_kktcsr *h, int64_t *indptr,
+                              int64_t *indices, int32_t mem);
+/* hess_values: kktcsr_nnz_triplets doubles laid out as for the Hessian
+ * operator; jac_values: opty_hip_nnz doubles in the CSR layout; sigma: num_free
+ * doubles or NULL; data: kktcsr_nnz doubles; all in `mem` memory, 8-byte
+ * alignment is enough.  Synchronous for OPTY_HIP_HOST (staged through buffers
+ * of the handle), enqueued on the problem's stream for OPTY_HIP_DEVICE.
+ * Refused before anything is enqueued: null hess_values / jac_values / data,
+ * a data range that overlaps an input, a bad memory kind. */
+int opty_hip_kktcsr_assemble(opty_hip_kktcsr *h, const double *hess_values,
+                             const double *jac_values, const double *sigma,
+                             double delta_w, double delta_c, double *data,
+                             int32_t mem);
+/* The same for OPTY_HIP_DEVICE pointers, synchronous, with device events
+ * around its four stages (measurements): stage_ms[0 .. 4) = milliseconds of
+ * the compression (opty_hesscsr + opty_hesscsr_fin), opty_kkt_diag,
+ * opty_kkt_jrows, opty_kkt_inst. */
+int opty_hip_kktcsr_assemble_timed(opty_hip_kktcsr *h,
+                                   const double *hess_values,
+                                   const double *jac_values,
+                                   const double *sigma, double delta_w,
+                                   double delta_c, double *data,
+                                   float *stage_ms);
 
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);

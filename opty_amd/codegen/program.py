@@ -706,11 +706,16 @@ class _HessianCsrPlan(object):
     ``codes``, their columns are ``row*N + p + off``; ``items``: ``(out,
     col, positions, long_codes)`` -- one output each, the sum of the values
     at ``positions`` (ascending) on top of, for a tail x tail pair with
-    per-node sources, the long sum of ``long_codes`` over all nodes."""
+    per-node sources, the long sum of ``long_codes`` over all nodes.
+
+    ``with_diagonal``: every row gets its diagonal pair -- an empty source
+    list for ``(R, 0)`` in every trajectory row class, in every whole row and
+    in every tail row --; a pair that no triplet hits has no addends and
+    evaluates to ``+0.0``.  The diagonal is the last entry of its row."""
 
     def __init__(self, N, num_rows, num_tail, pattern, inst_rows=(),
                  inst_cols=(), obj_pattern=(), obj_base=0, tail_rows=(),
-                 tail_cols=()):
+                 tail_cols=(), with_diagonal=False):
         import numpy as np
         N = self.N = int(N)
         ncn = self.ncn = N - 1
@@ -749,6 +754,9 @@ class _HessianCsrPlan(object):
                 segs[a[1]].setdefault(b[0], []).append(2*e + b[1])
             else:
                 longs[a[1]].setdefault(b[1], []).append(2*e)
+        if with_diagonal:
+            for R in range(num_rows):
+                traj[R].setdefault((R, 0), [])
 
         def in_order(codes):
             # ascending position in ``values``: node section, node p - 1
@@ -761,7 +769,7 @@ class _HessianCsrPlan(object):
 
         def traj_row(R, p):
             """{column: positions} of the regular pattern of row (R, p)."""
-            out = {}
+            out = {R*N + p: []} if with_diagonal else {}
             for (Rp, d), codes in traj[R].items():
                 v = valid(codes, p)
                 if v:
@@ -801,6 +809,8 @@ class _HessianCsrPlan(object):
                 hi = ncn if any(c & 1 for c in codes) else ncn - 1
                 seg.append([Rp, lo, hi, codes, {}])
             extra, tcols = {}, {jp: [] for jp in longs[j]}
+            if with_diagonal:
+                tcols.setdefault(j, [])
             for c, at in explicit.get(tail + j, {}).items():
                 if c >= tail:
                     tcols.setdefault(c - tail, []).extend(at)
@@ -900,7 +910,7 @@ class _HessianCsrPlan(object):
 
 def hessian_csr_structure(N, num_rows, num_tail, pattern, inst_rows=(),
                           inst_cols=(), obj_pattern=(), obj_base=0,
-                          tail_rows=(), tail_cols=()):
+                          tail_rows=(), tail_cols=(), with_diagonal=False):
     """``(indptr, indices, slot)`` (int64) of the Hessian's lower triangle in
     compressed-sparse-row form over ``num_rows*N + num_tail`` rows: exactly
     the distinct ``(row, col)`` pairs of the triplets ``[node section (i*PH +
@@ -916,11 +926,14 @@ def hessian_csr_structure(N, num_rows, num_tail, pattern, inst_rows=(),
     sub-list at the first and the last --; a tail row is one segment of
     consecutive time nodes per trajectory row it couples with, then its tail
     columns.  Explicit triplets (instance, parameter-parameter) fall on a
-    pair of the pattern or add a column to their row."""
+    pair of the pattern or add a column to their row.
+
+    ``with_diagonal=True``: every row also holds its diagonal pair, last in
+    the row, whether or not a triplet lands on it."""
     import numpy as np
     plan = _HessianCsrPlan(N, num_rows, num_tail, pattern, inst_rows,
                            inst_cols, obj_pattern, obj_base, tail_rows,
-                           tail_cols)
+                           tail_cols, with_diagonal)
     indices = np.full(plan.nnz_unique, -1, dtype=np.int64)
     slot = np.full(plan.nnz, -1, dtype=np.int64)
     every = np.arange(plan.ncn, dtype=np.int64)
@@ -940,7 +953,8 @@ def hessian_csr_structure(N, num_rows, num_tail, pattern, inst_rows=(),
 
 def assemble_hessian_csr(N, num_rows, num_tail, values, pattern,
                          inst_rows=(), inst_cols=(), obj_pattern=(),
-                         obj_base=0, tail_rows=(), tail_cols=()):
+                         obj_base=0, tail_rows=(), tail_cols=(),
+                         with_diagonal=False):
     """``data`` of the CSR lower triangle of :func:`hessian_csr_structure`
     from the triplets ``values``: element ``u`` is the sum of the triplets of
     pair ``u``.  The host statement of ``opty_hesscsr`` / ``opty_hesscsr_fin``:
@@ -948,11 +962,12 @@ def assemble_hessian_csr(N, num_rows, num_tail, values, pattern,
     ``+0.0`` (the bits of ``np.add.at``); a long group -- a tail x tail pair
     with a triplet per constraint node -- adds the block partials of
     :meth:`_HessianCsrPlan.long_sum` in block order, then its explicit
-    triplets in stored order."""
+    triplets in stored order.  ``with_diagonal=True``: the structure with
+    every diagonal pair; one that no triplet hits is ``+0.0``."""
     import numpy as np
     plan = _HessianCsrPlan(N, num_rows, num_tail, pattern, inst_rows,
                            inst_cols, obj_pattern, obj_base, tail_rows,
-                           tail_cols)
+                           tail_cols, with_diagonal)
     values = np.asarray(values, dtype=float)
     assert values.shape == (plan.nnz,)
     data = np.zeros(plan.nnz_unique)
@@ -966,6 +981,149 @@ def assemble_hessian_csr(N, num_rows, num_tail, values, pattern,
         for k in at:
             x = x + values[k]
         data[out] = x
+    return data
+
+
+class _KktCsrPlan(object):
+    """Where everything goes in the CSR lower triangle of the augmented
+    system ``[[W + diag(sigma) + delta_w I, J^T], [J, -delta_c I]]`` over
+    ``n + m`` rows (:func:`kkt_csr_structure`), in closed form: the ``W``
+    part is the Hessian's plan with every diagonal; Jacobian row ``(j, i)``
+    of a ``layout='csr'`` program ``prog`` has length ``L_j + 1`` and starts
+    at ``nnzW + (S_j + j)*(N-1) + i*(L_j + 1)``, its diagonal is its last
+    slot; the instance rows (``jac_inst_rows`` / ``jac_inst_cols``: global
+    constraint rows and free columns, sorted by row then column) follow.
+
+    ``hess``: the Hessian's plan; ``nnz_w``: its pairs; ``w_diag``: position
+    of the diagonal of every free row; ``jac_slot``: position in ``data`` of
+    every Jacobian value; ``con_diag``: position of the diagonal of every
+    constraint row."""
+
+    def __init__(self, prog, N, pattern, inst_rows=(), inst_cols=(),
+                 obj_pattern=(), obj_base=0, tail_rows=(), tail_cols=(),
+                 jac_inst_rows=(), jac_inst_cols=()):
+        import numpy as np
+        if getattr(prog, 'layout', None) != 'csr':
+            raise ValueError("the augmented system as CSR needs a program "
+                             "with jacobian_layout='csr'.")
+        N = self.N = int(N)
+        ncn = N - 1
+        nrows, ntail = prog.n + prog.q, prog.r + prog.s
+        hess = self.hess = _HessianCsrPlan(
+            N, nrows, ntail, pattern, inst_rows, inst_cols, obj_pattern,
+            obj_base, tail_rows, tail_cols, with_diagonal=True)
+        n = self.n = hess.num_free
+        nnz_w = self.nnz_w = hess.nnz_unique
+        self.w_diag = hess.indptr[1:] - 1
+        M, P = prog.M, len(prog.pattern)
+        rs = np.asarray(prog.row_start, dtype=np.int64)
+        num_inst = len(prog.inst_con_out)
+        irows = np.asarray(jac_inst_rows, dtype=np.int64).reshape(-1) - M*ncn
+        icols = np.asarray(jac_inst_cols, dtype=np.int64).reshape(-1)
+        if len(irows) != len(prog.inst_jac_out) or len(icols) != len(irows):
+            raise ValueError('%d instance rows / %d columns for %d instance '
+                             'entries' % (len(irows), len(icols),
+                                          len(prog.inst_jac_out)))
+        if np.any((irows < 0) | (irows >= num_inst) | (icols < 0) |
+                  (icols >= n)):
+            raise ValueError('instance entry outside the problem')
+        if np.any(np.diff(irows*n + icols) <= 0):
+            raise ValueError('the instance entries are not sorted by row, '
+                             'then column')
+        m = self.m = M*ncn + num_inst
+        counts = np.bincount(irows, minlength=num_inst).astype(np.int64)
+        lens = np.concatenate((np.repeat(np.diff(rs) + 1, ncn), counts + 1))
+        self.indptr = np.concatenate(
+            (hess.indptr, nnz_w + np.cumsum(lens))).astype(np.int64)
+        self.nnz = int(self.indptr[-1])
+        self.jac_nnz = P*ncn + len(irows)
+
+        i = np.arange(ncn, dtype=np.int64)
+        tail = nrows*N
+        indices = np.full(self.nnz, -1, dtype=np.int64)
+        jac_slot = np.empty(self.jac_nnz, dtype=np.int64)
+        for j in range(M):
+            S, L = int(rs[j]), int(rs[j + 1] - rs[j])
+            start = nnz_w + (S + j)*ncn + i*(L + 1)
+            for c in range(L):
+                jj, k = prog.pattern[S + c]
+                assert jj == j
+                row, off = column_side(prog.n, prog.q, prog.method, k)
+                indices[start + c] = row*N + i + off if row >= 0 \
+                    else tail + off
+                jac_slot[S*ncn + i*L + c] = start + c
+            indices[start + L] = n + j*ncn + i
+        first = np.concatenate(([0], np.cumsum(counts)))[:-1]
+        base = nnz_w + (P + M)*ncn
+        start = base + first + np.arange(num_inst, dtype=np.int64)
+        at = start[irows] + np.arange(len(irows), dtype=np.int64) \
+            - first[irows]
+        indices[at] = icols
+        jac_slot[P*ncn:] = at
+        indices[start + counts] = n + M*ncn + np.arange(num_inst)
+        self.indices, self.jac_slot = indices, jac_slot
+        self.con_diag = self.indptr[n + 1:] - 1
+
+
+def kkt_csr_structure(prog, N, pattern, inst_rows=(), inst_cols=(),
+                      obj_pattern=(), obj_base=0, tail_rows=(), tail_cols=(),
+                      jac_inst_rows=(), jac_inst_cols=()):
+    """``(indptr, indices)`` (int64) of the lower triangle of the augmented
+    system ``K = [[W + diag(sigma) + delta_w I, J^T], [J, -delta_c I]]`` in
+    compressed-sparse-row form over ``num_free + num_constraints`` rows.
+    Row ``r < num_free``: the columns of row ``r`` of
+    :func:`hessian_csr_structure` (its arguments are ``N, n + q, r + s`` of
+    ``prog`` and ``pattern`` ...) and the diagonal ``(r, r)``, stored whether
+    or not a triplet lands on it.  Row ``num_free + k``: the columns of row
+    ``k`` of the CSR Jacobian of ``prog`` (``layout='csr'``; ``jac_inst_rows``
+    / ``jac_inst_cols``: the indices of its instance entries), then the
+    diagonal.  Every diagonal is the last entry of its row.  Closed form:
+    nothing of the size of the matrix is sorted."""
+    import numpy as np
+    plan = _KktCsrPlan(prog, N, pattern, inst_rows, inst_cols, obj_pattern,
+                       obj_base, tail_rows, tail_cols, jac_inst_rows,
+                       jac_inst_cols)
+    indices = plan.indices
+    w = hessian_csr_structure(
+        N, prog.n + prog.q, prog.r + prog.s, pattern, inst_rows, inst_cols,
+        obj_pattern, obj_base, tail_rows, tail_cols, with_diagonal=True)[1]
+    indices[:plan.nnz_w] = w
+    assert np.all(indices >= 0)
+    return plan.indptr, indices
+
+
+def assemble_kkt_csr(prog, N, hess_values, jac_values, pattern, inst_rows=(),
+                     inst_cols=(), obj_pattern=(), obj_base=0, tail_rows=(),
+                     tail_cols=(), jac_inst_rows=(), jac_inst_cols=(),
+                     sigma=None, delta_w=0.0, delta_c=0.0):
+    """``data`` of :func:`kkt_csr_structure` from the Hessian's triplets
+    ``hess_values`` and the values ``jac_values`` of the CSR Jacobian.  The
+    host statement of ``opty_kkt_diag`` / ``opty_kkt_jrows`` /
+    ``opty_kkt_inst`` behind ``opty_hesscsr``: an off-diagonal of the ``W``
+    block has the bits of :func:`assemble_hessian_csr`; a diagonal of the
+    ``W`` block is ``(h + sigma_r) + delta_w`` rounded in that order, ``h``
+    the compressed element (``+0.0`` where no triplet lands), ``sigma_r``
+    ``+0.0`` without ``sigma``; a Jacobian entry is copied; a diagonal of the
+    constraint block is ``0.0 - delta_c``."""
+    import numpy as np
+    plan = _KktCsrPlan(prog, N, pattern, inst_rows, inst_cols, obj_pattern,
+                       obj_base, tail_rows, tail_cols, jac_inst_rows,
+                       jac_inst_cols)
+    jac_values = np.asarray(jac_values, dtype=float)
+    if jac_values.shape != (plan.jac_nnz,):
+        raise ValueError('jac_values must have shape (%d,)' % plan.jac_nnz)
+    sigma = np.zeros(plan.n) if sigma is None else \
+        np.asarray(sigma, dtype=float)
+    if sigma.shape != (plan.n,):
+        raise ValueError('sigma must have shape (%d,)' % plan.n)
+    data = np.empty(plan.nnz)
+    data[:plan.nnz_w] = assemble_hessian_csr(
+        N, prog.n + prog.q, prog.r + prog.s, hess_values, pattern, inst_rows,
+        inst_cols, obj_pattern, obj_base, tail_rows, tail_cols,
+        with_diagonal=True)
+    data[plan.w_diag] = (data[plan.w_diag] + sigma) + float(delta_w)
+    data[plan.jac_slot] = jac_values
+    data[plan.con_diag] = 0.0 - float(delta_c)
     return data
 
 

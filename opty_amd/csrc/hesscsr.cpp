@@ -52,6 +52,12 @@
 // kinds.  Every element of data is stored exactly once, by opty_hesscsr or by
 // the item that owns it; no atomics; nothing outside data (and the handle's
 // partials) is written.
+//
+// WITH EVERY DIAGONAL (opty_hip_hesscsr_create_with_diagonal, what kktcsr.cpp
+// builds on): an empty source list for (R, 0) in every trajectory row class,
+// in every whole row and in every tail row.  (R, 0) is the largest key of a
+// class of the lower triangle, so the diagonal is the last column of its row;
+// an output without sources is stored as +0.0 by the loops above as they are.
 #include "opty_internal.h"
 
 #include <cstdint>
@@ -294,11 +300,12 @@ struct opty_hip_hesscsr : Borrowed {
     }
 };
 
-extern "C" {
-
-int opty_hip_hesscsr_create(opty_hip_problem *p,
-                            const opty_hip_hessmv_desc *desc,
-                            opty_hip_hesscsr **out) {
+// Both create entry points.  with_diagonal: every row gets its diagonal pair
+// -- an EMPTY source list for (R, 0) in every trajectory row class, in every
+// whole row that items own and in every tail row --, so that a pair that no
+// triplet hits is stored as +0.0 by the kernels as they are.
+static int create_impl(opty_hip_problem *p, const opty_hip_hessmv_desc *desc,
+                       bool with_diagonal, opty_hip_hesscsr **out) {
     if (!p || !desc || !out) return fail("null argument");
     if (int rc = check_hessmv_desc(p, desc)) return rc;
     const int nrows = p->d.n + p->d.q, ntail = p->d.r + p->d.s;
@@ -332,6 +339,8 @@ int opty_hip_hesscsr_create(opty_hip_problem *p,
         else if (rb >= 0) segs[oa][rb].push_back(2*e + ob);
         else longs[oa][ob].push_back(2*e);
     }
+    if (with_diagonal)
+        for (int R = 0; R < nrows; ++R) traj[R][{R, 0}];
     // ascending position in `values`: node section, node p - 1 before node
     // p; then the objective section, entry-major
     auto in_order = [&](std::vector<int> codes) {
@@ -354,6 +363,7 @@ int opty_hip_hesscsr_create(opty_hip_problem *p,
     // the regular pattern of trajectory row (R, at)
     auto traj_row = [&](int R, long long at) {
         Row row;
+        if (with_diagonal) row[(long long)R*N + at];
         for (const auto &kv : traj[R])
             for (int c : in_order(kv.second))
                 if (exists(c, at))
@@ -475,6 +485,7 @@ int opty_hip_hesscsr_create(opty_hip_problem *p,
             pieces[(long long)s.Rp*N + s.lo] = s;
         }
         for (const auto &kv : longs[j]) tcols[kv.first];
+        if (with_diagonal) tcols[j];
         auto found = explicit_.find(tail + j);
         if (found != explicit_.end())
             for (const auto &cv : found->second) {
@@ -645,6 +656,20 @@ int opty_hip_hesscsr_create(opty_hip_problem *p,
     }
     *out = h;
     return 0;
+}
+
+extern "C" {
+
+int opty_hip_hesscsr_create(opty_hip_problem *p,
+                            const opty_hip_hessmv_desc *desc,
+                            opty_hip_hesscsr **out) {
+    return create_impl(p, desc, false, out);
+}
+
+int opty_hip_hesscsr_create_with_diagonal(opty_hip_problem *p,
+                                          const opty_hip_hessmv_desc *desc,
+                                          opty_hip_hesscsr **out) {
+    return create_impl(p, desc, true, out);
 }
 
 int opty_hip_hesscsr_destroy(opty_hip_hesscsr *h) {

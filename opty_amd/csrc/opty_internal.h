@@ -16,6 +16,10 @@
 //                     triplets; borrows too, kernels of its own)
 //   hesscsr.cpp       the CSR-Hessian handle (the triplets compressed to the
 //                     unique lower triangle; borrows too, kernels of its own)
+//   kktcsr.cpp        the augmented-system handle (CSR Hessian with every
+//                     diagonal and CSR Jacobian as one CSR lower triangle;
+//                     borrows too, owns a CSR-Hessian handle, kernels of
+//                     its own)
 //   referee.cpp       (libopty_hip_referee.so) instruction-tape kernel and
 //                     register poisoner of the build verification
 #pragma once
@@ -142,6 +146,10 @@ struct opty_hip_problem {
     long long *d_inst_idx = nullptr, *d_inst_rows = nullptr,
               *d_inst_cols = nullptr;
     int *d_pattern = nullptr;   // (j, k) per stored block entry when pruned
+    // host copies of that pattern and of the instance entries' indices, for
+    // the handles that lay the Jacobian out again (kktcsr.cpp)
+    std::vector<int32_t> block_jk;
+    std::vector<int64_t> inst_rows_host, inst_cols_host;
     int *d_rowinfo = nullptr;   // (S_j, L_j) per stored block entry (CSR)
     double *d_free = nullptr, *d_con = nullptr, *d_jac = nullptr;  // staging
     double *d_con_scratch = nullptr;    // jac_via_fused: discarded values

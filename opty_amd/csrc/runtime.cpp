@@ -1224,6 +1224,8 @@ int opty_hip_set_instance_indices(opty_hip_problem *p,
                           hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(p->d_inst_cols, cols, nz*sizeof(int64_t),
                           hipMemcpyHostToDevice));
+        p->inst_rows_host.assign(rows, rows + nz);
+        p->inst_cols_host.assign(cols, cols + nz);
     }
     p->have_inst = true;
     return 0;
@@ -1241,6 +1243,7 @@ int opty_hip_set_block_pattern(opty_hip_problem *p, const int32_t *jk) {
     if (int rc = ensure(&p->d_pattern, (size_t)2*p->d.P)) return rc;
     HIP_TRY(hipMemcpy(p->d_pattern, jk, 2*p->d.P*sizeof(int32_t),
                       hipMemcpyHostToDevice));
+    p->block_jk.assign(jk, jk + 2*(size_t)p->d.P);
     if (p->d.layout == OPTY_HIP_LAYOUT_CSR) {
         std::vector<int32_t> info(2*(size_t)p->d.P);
         for (int e = 0; e < p->d.P;) {

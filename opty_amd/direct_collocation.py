@@ -1867,6 +1867,214 @@ class ConstraintCollocator(object):
         evaluate.compress = compress
         return evaluate
 
+    # ------------------------------------------------------------------
+    # Augmented system as CSR
+    # ------------------------------------------------------------------
+    def _require_csr_layout(self, what):
+        if self._jacobian_layout != 'csr':
+            raise ValueError("%s needs jacobian_layout='csr'." % what)
+
+    def _ensure_kktcsr(self, objective=None):
+        """The augmented-system handle (made on first use; one for the
+        constraint triplets alone, one per objective Hessian handle)."""
+        attr = '_kktcsr' if objective is None else '_kktcsr_objective'
+        if objective is not None and \
+                getattr(self, '_kktcsr_objective_of', None) is not objective:
+            old = getattr(self, attr, None)
+            if old is not None:
+                old.release()
+            setattr(self, attr, None)
+            self._kktcsr_objective_of = objective
+
+        def create(hip):
+            return hb.HipKktCsr(hip, self._hessmv_descriptor(objective)), {}
+        # (no program of its own: the assembly is checked against NumPy and
+        # scipy.sparse by the test suite)
+        return self._ensure_derived(attr, create, lambda handle: None)
+
+    @staticmethod
+    def _kkt_csr_structure_of(handle):
+        """``(indptr, indices)`` (int64) from ``handle``'s closed form."""
+        hip = handle._problem
+        indptr = np.empty(hip.num_free + hip.num_constraints + 1,
+                          dtype=np.int64)
+        indices = np.empty(handle.nnz_kkt, dtype=np.int64)
+        handle.structure(indptr, indices, hb.HOST)
+        return indptr, indices
+
+    def kkt_csr_structure(self):
+        """``(indptr, indices)`` (int64) of the lower triangle of the
+        augmented system ``K = [[W + diag(sigma) + delta_w I, J^T], [J,
+        -delta_c I]]`` -- ``W`` the constraint part of the Hessian of the
+        Lagrangian, ``J`` the constraint Jacobian -- in compressed-sparse-row
+        form over ``num_free + num_constraints`` rows.  Row ``r < num_free``:
+        the columns of row ``r`` of :meth:`hessian_csr_structure` and the
+        diagonal, stored whether or not a triplet lands on it; row ``num_free
+        + k``: the columns of row ``k`` of :meth:`jacobian_csr_structure`,
+        then the diagonal.  Every diagonal is the last entry of its row; the
+        values of :meth:`generate_kkt_csr_function` are ``data`` of
+        ``scipy.sparse.csr_matrix((data, indices, indptr))`` as they are
+        (``has_canonical_format``).  Needs ``jacobian_layout='csr'``."""
+        # (refused before a device is asked for)
+        self._require_csr_layout('kkt_csr_structure')
+        self._build_hessian_program()
+        self._ensure_hessian()
+        return self._kkt_csr_structure_of(self._ensure_kktcsr())
+
+    def _kkt_csr_assemble(self, handle):
+        """``assemble(hess_values, jac_values, sigma=None, delta_w=0.0,
+        delta_c=0.0) -> data`` over ``handle``: host arrays in, a persistent
+        page-locked array out; torch CUDA tensors in, a new CUDA tensor
+        out."""
+        hip = self._hip
+        nfree, nh, nj, nk = (self.num_free, handle.nnz, hip.nnz,
+                             handle.nnz_kkt)
+        result = hb.pinned_empty(nk)
+
+        def assemble(hess_values, jac_values, sigma=None, delta_w=0.0,
+                     delta_c=0.0):
+            if hasattr(hess_values, 'data_ptr'):
+                import torch
+                if tuple(hess_values.shape) != (nh,) or \
+                        tuple(jac_values.shape) != (nj,) or \
+                        (sigma is not None and
+                         tuple(sigma.shape) != (nfree,)):
+                    raise ValueError('hess_values / jac_values / sigma have '
+                                     'the wrong shape')
+                dev = hess_values.device
+                hess_values = hess_values.to(torch.float64).contiguous()
+                jac_values = jac_values.to(
+                    device=dev, dtype=torch.float64).contiguous()
+                if sigma is not None:
+                    sigma = torch.as_tensor(sigma).to(
+                        device=dev, dtype=torch.float64).contiguous()
+                out = torch.empty(nk, dtype=torch.float64, device=dev)
+                torch.cuda.current_stream(dev).synchronize()
+                handle.assemble(hess_values, jac_values, sigma, delta_w,
+                                delta_c, out, hb.DEVICE)
+                hip.synchronize()
+                return out
+            hess_values = np.ascontiguousarray(hess_values, dtype=np.float64)
+            jac_values = np.ascontiguousarray(jac_values, dtype=np.float64)
+            if hess_values.shape != (nh,):
+                raise ValueError('hess_values must have shape ({},), got {}'
+                                 .format(nh, hess_values.shape))
+            if jac_values.shape != (nj,):
+                raise ValueError('jac_values must have shape ({},), got {}'
+                                 .format(nj, jac_values.shape))
+            if sigma is not None:
+                sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+                if sigma.shape != (nfree,):
+                    raise ValueError('sigma must have shape ({},), got {}'
+                                     .format(nfree, sigma.shape))
+            handle.assemble(hess_values, jac_values, sigma, delta_w, delta_c,
+                            result, hb.HOST)
+            return result
+        assemble.result = result
+        return assemble
+
+    def _kkt_csr_function(self, handle, hessian_into):
+        """``kkt(free, lagrange, ..., sigma, delta_w, delta_c) -> data`` over
+        ``handle``; ``hessian_into(free, lagrange, values, *extra)`` fills
+        the device buffer ``values`` with the Hessian's triplets."""
+        hip = self._hip
+        nfree, ncon = self.num_free, self.num_constraints
+        assemble = self._kkt_csr_assemble(handle)
+        own = {}
+
+        def evaluate(free, lagrange, *extra, sigma=None, delta_w=0.0,
+                     delta_c=0.0):
+            if hasattr(free, 'data_ptr'):
+                import torch
+                if tuple(free.shape) != (nfree,) or \
+                        tuple(lagrange.shape) != (ncon,):
+                    raise ValueError('free / lagrange have the wrong shape')
+                if sigma is not None and tuple(sigma.shape) != (nfree,):
+                    raise ValueError('sigma has the wrong shape')
+                free = free.to(torch.float64).contiguous()
+                lagrange = lagrange.to(device=free.device,
+                                       dtype=torch.float64).contiguous()
+                self._sync_known(hip, free.cpu().numpy()
+                                 if self._callable_known else None)
+                bufs = own.get('torch')
+                if bufs is None or bufs[0].device != free.device:
+                    bufs = own['torch'] = tuple(
+                        torch.empty(k, dtype=torch.float64,
+                                    device=free.device)
+                        for k in (handle.nnz, hip.nnz))
+                values, jac = bufs
+                torch.cuda.current_stream(free.device).synchronize()
+                hessian_into(free, lagrange, values, *extra)
+                hip.eval_jac(free, jac, hb.DEVICE)
+                return assemble(values, jac, sigma, delta_w, delta_c)
+            free = self._host_free(free)
+            lagrange = np.ascontiguousarray(lagrange, dtype=np.float64)
+            if lagrange.shape != (ncon,):
+                raise ValueError('lagrange must have shape ({},), got {}'
+                                 .format(ncon, lagrange.shape))
+            if sigma is not None:
+                sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+                if sigma.shape != (nfree,):
+                    raise ValueError('sigma must have shape ({},), got {}'
+                                     .format(nfree, sigma.shape))
+            self._sync_known(hip, free)
+            if 'host' not in own:
+                own['host'] = tuple(
+                    hb.DeviceVector(np.zeros(k), self._device)
+                    for k in (nfree, ncon, handle.nnz, hip.nnz, nfree,
+                              handle.nnz_kkt))
+            d_free, d_lam, d_values, d_jac, d_sigma, d_data = own['host']
+            d_free.assign(free)
+            d_lam.assign(lagrange)
+            if sigma is not None:
+                d_sigma.assign(sigma)
+            hessian_into(d_free, d_lam, d_values, *extra)
+            hip.eval_jac(d_free, d_jac, hb.DEVICE)
+            handle.assemble(d_values, d_jac,
+                            None if sigma is None else d_sigma, delta_w,
+                            delta_c, d_data, hb.DEVICE)
+            hip.synchronize()
+            return d_data.read_into(assemble.result)
+        evaluate.handle = handle
+        evaluate.assemble = assemble
+        return evaluate
+
+    def generate_kkt_csr_function(self):
+        """Returns ``kkt(free, lagrange, sigma=None, delta_w=0.0,
+        delta_c=0.0) -> ndarray``: ``data`` of :meth:`kkt_csr_structure`, the
+        lower triangle of the augmented system assembled on the GPU.  The
+        triplets of :meth:`generate_hessian_function` and the Jacobian's
+        values are evaluated into device buffers that the function owns and
+        never leave the device.  An off-diagonal entry of the ``W`` block has
+        the bits of :meth:`generate_hessian_csr_function`'s element, a
+        diagonal is ``(h + sigma_r) + delta_w`` (``h`` = ``+0.0`` where no
+        triplet lands), a Jacobian entry has the bits of
+        ``generate_jacobian_function()(free)``, a diagonal of the constraint
+        block is ``0.0 - delta_c``; the same inputs give the same bits.  The
+        result is a persistent page-locked buffer that the next call
+        overwrites.
+
+        ``free``, ``lagrange`` and ``sigma`` may also be torch CUDA tensors;
+        the result is then a new CUDA tensor (nothing crosses PCIe).
+        ``kkt.assemble(hess_values, jac_values, sigma=None, delta_w=0.0,
+        delta_c=0.0)`` does the same for values the caller already holds.
+        Needs ``jacobian_layout='csr'``."""
+        self._require_csr_layout('generate_kkt_csr_function')
+        self._build_hessian_program()
+        hess = self._ensure_hessian()
+        handle = self._ensure_kktcsr()
+        kkt = self._kkt_csr_function(
+            handle, lambda free, lagrange, values: hess.evaluate(
+                free, lagrange, values, hb.DEVICE))
+
+        def evaluate(free, lagrange, sigma=None, delta_w=0.0, delta_c=0.0):
+            return kkt(free, lagrange, sigma=sigma, delta_w=delta_w,
+                       delta_c=delta_c)
+        evaluate.handle = handle
+        evaluate.assemble = kkt.assemble
+        evaluate.__doc__ = 'data of kkt_csr_structure() at (free, lagrange).'
+        return evaluate
+
     def generate_source(self):
         """HIP source of this problem's kernels and its launch metadata."""
         return self._emit(self._printer_options())
@@ -3705,6 +3913,63 @@ class Problem(object):
         self.hessian_csr_structure = hessian_csr_structure
         self.hessian_csr = hessian_csr
 
+        def kkt_csr_structure():
+            """``(indptr, indices)`` (int64) of the lower triangle of the
+            augmented system ``[[W + diag(sigma) + delta_w I, J^T], [J,
+            -delta_c I]]`` over ``num_free + num_constraints`` rows, ``W``
+            the Hessian of the Lagrangian over the ``[constraint |
+            objective]`` triplets, every diagonal stored and last in its row
+            (:meth:`ConstraintCollocator.kkt_csr_structure`).  Needs
+            ``jacobian_layout='csr'`` and a device-backed ``obj_hessian``."""
+            col._require_csr_layout('Problem.kkt_csr_structure')
+            handle = col._ensure_kktcsr(objective_handle('kkt_csr_structure'))
+            return col._kkt_csr_structure_of(handle)
+
+        kkt = {}
+
+        def hessian_into(free, lagrange, out, obj_factor):
+            # the constraint section on the collocator's stream, the
+            # objective's on torch's: the assembly waits for both
+            col._ensure_hessian().evaluate(free, lagrange, out[:num_con],
+                                           hb.DEVICE)
+            values(free, obj_factor, out[num_con:])
+
+        def kkt_csr(free, lagrange, obj_factor=1.0, sigma=None, delta_w=0.0,
+                    delta_c=0.0):
+            """``data`` of ``kkt_csr_structure()`` at ``(free, lagrange,
+            obj_factor)``, assembled on the GPU from the triplets of
+            ``hessian(...)`` and the Jacobian's values, none of which leaves
+            the device
+            (:meth:`ConstraintCollocator.generate_kkt_csr_function`): a
+            diagonal of the ``W`` block is ``(h + sigma_r) + delta_w``, one
+            of the constraint block ``0.0 - delta_c``.  Host arrays in: a
+            persistent page-locked array out; torch CUDA tensors in: a new
+            CUDA tensor out."""
+            col._require_csr_layout('Problem.kkt_csr')
+            handle = col._ensure_kktcsr(objective_handle('kkt_csr'))
+            if kkt.get('handle') is not handle:
+                kkt.update(handle=handle, function=col._kkt_csr_function(
+                    handle, hessian_into))
+            function = kkt['function']
+            if hasattr(free, 'data_ptr'):
+                return function(free, lagrange, obj_factor, sigma=sigma,
+                                delta_w=delta_w, delta_c=delta_c)
+            import torch
+            device = torch.device('cuda', col._device)
+            free = col._host_free(free)
+            lagrange = np.ascontiguousarray(lagrange, dtype=np.float64)
+            if sigma is not None:
+                sigma = torch.from_numpy(np.ascontiguousarray(
+                    sigma, dtype=np.float64)).to(device)
+            out = function(torch.from_numpy(free).to(device),
+                           torch.from_numpy(lagrange).to(device), obj_factor,
+                           sigma=sigma, delta_w=delta_w, delta_c=delta_c)
+            result = function.assemble.result
+            result[:] = out.cpu().numpy()
+            return result
+        self.kkt_csr_structure = kkt_csr_structure
+        self.kkt_csr = kkt_csr
+
     bounds = property(lambda self: self._bounds)
     eom_bounds = property(lambda self: self._eom_bounds)
 
@@ -3970,6 +4235,16 @@ class ShardedProblem(Problem):
     def hessian_csr(self, free, lagrange, obj_factor=1.0):
         raise NotImplementedError('the Hessian is not sharded: '
                                   'ShardedProblem has no hessian_csr.')
+
+    def kkt_csr_structure(self):
+        raise NotImplementedError(
+            'the Hessian is not sharded: ShardedProblem has no '
+            'kkt_csr_structure.')
+
+    def kkt_csr(self, free, lagrange, obj_factor=1.0, sigma=None,
+                delta_w=0.0, delta_c=0.0):
+        raise NotImplementedError('the Hessian is not sharded: '
+                                  'ShardedProblem has no kkt_csr.')
 
     def _install_hessian(self, obj_hessian):
         """``hessianstructure()`` and ``hessian(free, lagrange,

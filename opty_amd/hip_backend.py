@@ -76,7 +76,7 @@ def _hipcc():
 #: where) and of the build referee's own library
 RUNTIME_SOURCES = ('runtime.cpp', 'programs.cpp', 'host_scatter.cpp',
                    'comm.cpp', 'hessian.cpp', 'jacprod.cpp', 'hessmv.cpp',
-                   'hesscsr.cpp')
+                   'hesscsr.cpp', 'kktcsr.cpp')
 REFEREE_SOURCES = ('referee.cpp',)
 REFEREE_PATH = os.path.join(_PKG, 'libopty_hip_referee.so')
 
@@ -611,6 +611,23 @@ _SIGNATURES = {
                                                   ctypes.c_int32]),
     'opty_hip_hesscsr_compress': (ctypes.c_int, [_P, _P, _P,
                                                  ctypes.c_int32]),
+    'opty_hip_hesscsr_create_with_diagonal': (
+        ctypes.c_int, [_P, ctypes.POINTER(_HessmvDesc), ctypes.POINTER(_P)]),
+    'opty_hip_kktcsr_create': (ctypes.c_int,
+                               [_P, ctypes.POINTER(_HessmvDesc),
+                                ctypes.POINTER(_P)]),
+    'opty_hip_kktcsr_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_kktcsr_nnz': (ctypes.c_int64, [_P]),
+    'opty_hip_kktcsr_nnz_hessian': (ctypes.c_int64, [_P]),
+    'opty_hip_kktcsr_nnz_triplets': (ctypes.c_int64, [_P]),
+    'opty_hip_kktcsr_structure': (ctypes.c_int, [_P, _P, _P,
+                                                 ctypes.c_int32]),
+    'opty_hip_kktcsr_assemble': (ctypes.c_int,
+                                 [_P, _P, _P, _P, ctypes.c_double,
+                                  ctypes.c_double, _P, ctypes.c_int32]),
+    'opty_hip_kktcsr_assemble_timed': (ctypes.c_int,
+                                       [_P, _P, _P, _P, ctypes.c_double,
+                                        ctypes.c_double, _P, _P]),
     'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
                                                 ctypes.c_int64]),
     'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
@@ -1615,3 +1632,49 @@ class HipHessianCsr(_HessianTripletsHandle):
     def compress(self, values, data, mem):
         _check(self._lib.opty_hip_hesscsr_compress(
             self._handle(), _ptr(values), _ptr(data), mem))
+
+
+class HipKktCsr(_HessianTripletsHandle):
+    """One ``opty_hip_kktcsr`` handle: the lower triangle of the augmented
+    system ``[[W + diag(sigma) + delta_w I, J^T], [J, -delta_c I]]`` of a
+    :class:`HipProblem` with ``jacobian_layout='csr'`` as one canonical CSR
+    matrix, every diagonal stored, assembled on the device from the
+    Hessian's triplets and the Jacobian's values
+    (:class:`_HessianTripletsHandle`; ``include/opty_hip.h``, "Augmented
+    system as CSR").  ``nnz`` counts the Hessian's triplets."""
+
+    _create, _destroy = 'opty_hip_kktcsr_create', 'opty_hip_kktcsr_destroy'
+    _nnz = 'opty_hip_kktcsr_nnz_triplets'
+
+    @property
+    def nnz_kkt(self):
+        """Stored values of ``K``: the length of ``indices`` and ``data``."""
+        return int(self._lib.opty_hip_kktcsr_nnz(self._handle()))
+
+    @property
+    def nnz_hessian(self):
+        """Stored values of the ``W`` block, diagonals included."""
+        return int(self._lib.opty_hip_kktcsr_nnz_hessian(self._handle()))
+
+    def structure(self, indptr, indices, mem):
+        _check(self._lib.opty_hip_kktcsr_structure(
+            self._handle(), _ptr(indptr), _ptr(indices), mem))
+
+    def assemble(self, hess_values, jac_values, sigma, delta_w, delta_c,
+                 data, mem):
+        _check(self._lib.opty_hip_kktcsr_assemble(
+            self._handle(), _ptr(hess_values), _ptr(jac_values),
+            None if sigma is None else _ptr(sigma), float(delta_w),
+            float(delta_c), _ptr(data), mem))
+
+    def assemble_timed(self, hess_values, jac_values, sigma, delta_w,
+                       delta_c, data):
+        """The same for device pointers, synchronous: ``(compression,
+        opty_kkt_diag, opty_kkt_jrows, opty_kkt_inst)`` in milliseconds by
+        device events (``opty_hip_kktcsr_assemble_timed``)."""
+        ms = np.zeros(4, dtype=np.float32)
+        _check(self._lib.opty_hip_kktcsr_assemble_timed(
+            self._handle(), _ptr(hess_values), _ptr(jac_values),
+            None if sigma is None else _ptr(sigma), float(delta_w),
+            float(delta_c), _ptr(data), _ptr(ms)))
+        return tuple(float(x) for x in ms)
