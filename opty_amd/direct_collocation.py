@@ -30,21 +30,15 @@ from .codegen.emit_hip import emit_module, EmitOptions
 from . import build_ladder as bl
 from . import hip_backend as hb
 from . import isa_check
+from .marshal import on_device, column_major, check_vector, host_vector, \
+    host_vectors, host_block, device_vector, device_vectors, device_block, \
+    wait_for_torch, call_vectors, call_block, tensor_operands
 
 __all__ = ['Problem', 'ConstraintCollocator', 'ShardedProblem']
 
 logger = logging.getLogger(__name__)
 
 _METHODS = ('backward euler', 'midpoint')
-
-
-def column_major(V):
-    """``V`` (two-dimensional, either memory order, any real dtype) as a
-    column-major float64 array: column ``c`` is the ``V.shape[0]`` contiguous
-    doubles at ``c*V.shape[0]``, what ``opty_hip_hessmv_apply_block`` takes
-    with ``ldv = V.shape[0]``.  A column-major float64 ``V`` is returned as
-    it is; anything else is copied once."""
-    return np.asfortranarray(V, dtype=np.float64)
 
 
 class ConstraintCollocator(object):
@@ -1238,42 +1232,8 @@ class ConstraintCollocator(object):
             handle.jvp_block if which == 'jvp' else handle.vjp_block
 
         def evaluate(free, X):
-            if hasattr(free, 'data_ptr'):
-                import torch
-                if tuple(free.shape) != (nfree,) or X.ndim != 2 or \
-                        X.shape[0] != nin:
-                    raise ValueError('free / %s have the wrong shape' % name)
-                free = free.to(torch.float64).contiguous()
-                # the columns of X are the rows of its transpose
-                cols = X.to(device=free.device,
-                            dtype=torch.float64).t().contiguous()
-                k = cols.shape[0]
-                if k == 1 or (launch is None and k):
-                    return torch.stack([single(free, col) for col in cols],
-                                       dim=1)
-                out = torch.empty((k, nout), dtype=torch.float64,
-                                  device=free.device)
-                if k:
-                    self._sync_known(hip, free.cpu().numpy()
-                                     if self._callable_known else None)
-                    torch.cuda.current_stream(free.device).synchronize()
-                    launch(free, cols, nin, out, nout, k, hb.DEVICE)
-                    hip.synchronize()
-                return out.t()
-            free = self._host_free(free)
-            if np.ndim(X) != 2 or np.shape(X)[0] != nin:
-                raise ValueError('{} must have shape ({}, k), got {}'.format(
-                    name, nin, np.shape(X)))
-            X = column_major(X)
-            k = X.shape[1]
-            out = np.empty((nout, k), dtype=np.float64, order='F')
-            if k == 1 or launch is None:
-                for c in range(k):
-                    out[:, c] = single(free, X[:, c])
-            elif k:
-                self._sync_known(hip, free)
-                launch(free, X, nin, out, nout, k, hb.HOST)
-            return out
+            return call_block(launch, (free, 'free', nfree), (X, name, nin),
+                              nout, hip.synchronize, self._sync_free, single)
         evaluate.handle = handle
         evaluate.width = 1 if handle is None else handle.width
         return evaluate
@@ -1317,32 +1277,9 @@ class ConstraintCollocator(object):
         result = hb.pinned_empty(nout)
 
         def evaluate(free, vec):
-            if hasattr(free, 'data_ptr'):
-                import torch
-                if tuple(free.shape) != (nfree,) or \
-                        tuple(vec.shape) != (nin,):
-                    raise ValueError('free / %s have the wrong shape' % name)
-                free = free.to(torch.float64).contiguous()
-                vec = vec.to(device=free.device,
-                             dtype=torch.float64).contiguous()
-                # (known trajectories given as functions of ``free`` are
-                # host callables: they alone need ``free`` on the host)
-                self._sync_known(hip, free.cpu().numpy()
-                                 if self._callable_known else None)
-                out = torch.empty(nout, dtype=torch.float64,
-                                  device=free.device)
-                torch.cuda.current_stream(free.device).synchronize()
-                launch(free, vec, out, hb.DEVICE)
-                hip.synchronize()
-                return out
-            free = self._host_free(free)
-            vec = np.ascontiguousarray(vec, dtype=np.float64)
-            if vec.shape != (nin,):
-                raise ValueError('{} must have shape ({},), got {}'.format(
-                    name, nin, vec.shape))
-            self._sync_known(hip, free)
-            launch(free, vec, result, hb.HOST)
-            return result
+            return call_vectors(
+                launch, ((free, 'free', nfree), (vec, name, nin)), result,
+                hip.synchronize, before=self._sync_free)
         evaluate.handle = handle
         return evaluate
 
@@ -1385,17 +1322,16 @@ class ConstraintCollocator(object):
                 self.generate_jvp_block_function(),
                 self.generate_vjp_block_function())
         jmm, jtmm = self._jacprod_block_functions
-        if hasattr(free, 'data_ptr'):
+        if on_device(free):
             import torch
             free = free.detach().clone()
 
             def apply(f, x):
-                x = torch.from_numpy(np.ascontiguousarray(
-                    x, dtype=np.float64).reshape(-1)).to(free.device)
-                return f(free, x).cpu().numpy()
+                # (the function takes a host vector to ``free``'s device)
+                return f(free, np.reshape(x, -1)).cpu().numpy()
 
             def apply_block(f, X):
-                if hasattr(X, 'data_ptr'):
+                if on_device(X):
                     return f(free, X)
                 X = torch.from_numpy(column_major(X).T).to(free.device).t()
                 return f(free, X).cpu().numpy()
@@ -1406,13 +1342,14 @@ class ConstraintCollocator(object):
                 return np.array(f(free, np.asarray(x).reshape(-1)))
 
             def apply_block(f, X):
-                if hasattr(X, 'data_ptr'):
+                if on_device(X):
                     import torch
                     return torch.from_numpy(np.ascontiguousarray(
                         f(free, X.detach().cpu().numpy()))).to(X.device)
                 return f(free, X)
 
-        class JacobianOperator(LinearOperator):
+        class JacobianOperator(tensor_operands('matmat', 'rmatmat'),
+                               LinearOperator):
             """``matmat`` / ``rmatmat`` are one block product each
             (:meth:`generate_jvp_block_function`); a CUDA block of vectors is
             taken as it is (SciPy would convert it to an array) and answered
@@ -1433,16 +1370,6 @@ class ConstraintCollocator(object):
 
             def _rmatmat(op, X):
                 return apply_block(jtmm, X)
-
-            def matmat(op, X):
-                if hasattr(X, 'data_ptr'):
-                    return apply_block(jmm, X)
-                return super().matmat(X)
-
-            def rmatmat(op, X):
-                if hasattr(X, 'data_ptr'):
-                    return apply_block(jtmm, X)
-                return super().rmatmat(X)
 
         return JacobianOperator()
 
@@ -1468,24 +1395,31 @@ class ConstraintCollocator(object):
                         tail_cols=tail + objective.tail_pairs[:, 1])
         return desc
 
-    def _ensure_hessmv(self, objective=None):
-        """The Hessian-product handle (made on first use; one for the
-        constraint triplets alone, one per objective Hessian handle)."""
-        attr = '_hessmv' if objective is None else '_hessmv_objective'
+    def _ensure_over_triplets(self, stem, cls, objective):
+        """The handle of class ``cls`` over the Hessian's triplets (made on
+        first use; ``self.<stem>`` for the constraint triplets alone,
+        ``self.<stem>_objective`` with those of the objective Hessian handle
+        ``self.<stem>_objective_of`` behind them: one per such handle)."""
+        attr = stem if objective is None else stem + '_objective'
         if objective is not None and \
-                getattr(self, '_hessmv_objective_of', None) is not objective:
+                getattr(self, attr + '_of', None) is not objective:
             old = getattr(self, attr, None)
             if old is not None:
                 old.release()
             setattr(self, attr, None)
-            self._hessmv_objective_of = objective
+            setattr(self, attr + '_of', objective)
 
         def create(hip):
-            return hb.HipHessianProduct(
-                hip, self._hessmv_descriptor(objective)), {}
-        # (no program of its own to hold the kernels to: the product is
-        # checked against the triplets by the test suite)
+            return cls(hip, self._hessmv_descriptor(objective)), {}
+        # (no program of its own to hold the kernels to: the handle is
+        # checked against NumPy and scipy.sparse on the triplets by the test
+        # suite)
         return self._ensure_derived(attr, create, lambda handle: None)
+
+    def _ensure_hessmv(self, objective=None):
+        """The Hessian-product handle."""
+        return self._ensure_over_triplets('_hessmv', hb.HipHessianProduct,
+                                          objective)
 
     def _hessmv_function(self, handle):
         """``hmv(values, v) -> y`` over ``handle``."""
@@ -1494,30 +1428,9 @@ class ConstraintCollocator(object):
         result = hb.pinned_empty(nfree)
 
         def evaluate(values, v):
-            if hasattr(values, 'data_ptr'):
-                import torch
-                if tuple(values.shape) != (nnz,) or \
-                        tuple(v.shape) != (nfree,):
-                    raise ValueError('values / v have the wrong shape')
-                values = values.to(torch.float64).contiguous()
-                v = v.to(device=values.device,
-                         dtype=torch.float64).contiguous()
-                out = torch.empty(nfree, dtype=torch.float64,
-                                  device=values.device)
-                torch.cuda.current_stream(values.device).synchronize()
-                handle.apply(values, v, out, hb.DEVICE)
-                hip.synchronize()
-                return out
-            values = np.ascontiguousarray(values, dtype=np.float64)
-            if values.shape != (nnz,):
-                raise ValueError('values must have shape ({},), got {}'
-                                 .format(nnz, values.shape))
-            v = np.ascontiguousarray(v, dtype=np.float64)
-            if v.shape != (nfree,):
-                raise ValueError('v must have shape ({},), got {}'.format(
-                    nfree, v.shape))
-            handle.apply(values, v, result, hb.HOST)
-            return result
+            return call_vectors(
+                handle.apply, ((values, 'values', nnz), (v, 'v', nfree)),
+                result, hip.synchronize)
         evaluate.handle = handle
         return evaluate
 
@@ -1528,37 +1441,8 @@ class ConstraintCollocator(object):
         nfree, nnz = self.num_free, handle.nnz
 
         def evaluate(values, V):
-            if hasattr(values, 'data_ptr'):
-                import torch
-                if tuple(values.shape) != (nnz,) or V.ndim != 2 or \
-                        V.shape[0] != nfree:
-                    raise ValueError('values / V have the wrong shape')
-                values = values.to(torch.float64).contiguous()
-                # the columns of V are the rows of its transpose
-                cols = V.to(device=values.device,
-                            dtype=torch.float64).t().contiguous()
-                k = cols.shape[0]
-                out = torch.empty((k, nfree), dtype=torch.float64,
-                                  device=values.device)
-                if k:
-                    torch.cuda.current_stream(values.device).synchronize()
-                    handle.apply_block(values, cols, nfree, out, nfree, k,
-                                       hb.DEVICE)
-                    hip.synchronize()
-                return out.t()
-            values = np.ascontiguousarray(values, dtype=np.float64)
-            if values.shape != (nnz,):
-                raise ValueError('values must have shape ({},), got {}'
-                                 .format(nnz, values.shape))
-            if np.ndim(V) != 2 or np.shape(V)[0] != nfree:
-                raise ValueError('V must have shape ({}, k), got {}'.format(
-                    nfree, np.shape(V)))
-            V = column_major(V)
-            Y = np.empty(V.shape, dtype=np.float64, order='F')
-            if V.shape[1]:
-                handle.apply_block(values, V, nfree, Y, nfree, V.shape[1],
-                                   hb.HOST)
-            return Y
+            return call_block(handle.apply_block, (values, 'values', nnz),
+                              (V, 'V', nfree), nfree, hip.synchronize)
         evaluate.handle = handle
         return evaluate
 
@@ -1598,59 +1482,45 @@ class ConstraintCollocator(object):
         from scipy.sparse.linalg import LinearOperator
         nfree = self.num_free
         hip = self._hip
-        if hasattr(values, 'data_ptr'):
+        if on_device(values):
             import torch
+            dev = values.device
 
             def apply(x):
-                on_device = hasattr(x, 'data_ptr')
-                if on_device:
-                    x = x.to(device=values.device,
-                             dtype=torch.float64).reshape(-1).contiguous()
-                else:
-                    x = torch.from_numpy(np.ascontiguousarray(
-                        x, dtype=np.float64).reshape(-1)).to(values.device)
-                if tuple(x.shape) != (nfree,):
-                    raise ValueError('v must have shape (%d,)' % nfree)
-                out = torch.empty(nfree, dtype=torch.float64,
-                                  device=values.device)
-                torch.cuda.current_stream(values.device).synchronize()
+                host = not on_device(x)
+                if host:
+                    x = torch.from_numpy(
+                        host_vector(np.reshape(x, -1), 'v', nfree))
+                x = device_vector(x.reshape(-1), 'v', nfree, dev)
+                out = torch.empty(nfree, dtype=torch.float64, device=dev)
+                wait_for_torch(dev)
                 handle.apply(values, x, out, hb.DEVICE)
                 hip.synchronize()
-                return out if on_device else out.cpu().numpy()
+                return out.cpu().numpy() if host else out
 
             def apply_block(X):
-                on_device = hasattr(X, 'data_ptr')
-                if not on_device:
-                    X = torch.from_numpy(column_major(X).T)
-                elif X.ndim == 2:
-                    X = X.t()
-                if X.ndim != 2 or X.shape[1] != nfree:
-                    raise ValueError('X must have shape (%d, k)' % nfree)
-                # (the columns of X: the rows of its transpose)
-                X = X.to(device=values.device,
-                         dtype=torch.float64).contiguous()
+                host = not on_device(X)
+                if host:
+                    X = torch.from_numpy(host_block(X, 'X', nfree))
+                X = device_block(X, 'X', nfree, dev)
                 k = X.shape[0]
-                out = torch.empty((k, nfree), dtype=torch.float64,
-                                  device=values.device)
+                out = torch.empty((k, nfree), dtype=torch.float64, device=dev)
                 if k:
-                    torch.cuda.current_stream(values.device).synchronize()
+                    wait_for_torch(dev)
                     handle.apply_block(values, X, nfree, out, nfree, k,
                                        hb.DEVICE)
                     hip.synchronize()
-                return out.t() if on_device else out.cpu().numpy().T
+                return out.cpu().numpy().T if host else out.t()
         else:
             values = hb.DeviceVector(values, self._device)
             d_v = hb.DeviceVector(np.zeros(nfree), self._device)
             d_y = hb.DeviceVector(np.zeros(nfree), self._device)
 
             def apply(x):
-                like = x if hasattr(x, 'data_ptr') else None
+                like = x if on_device(x) else None
                 if like is not None:
                     x = x.detach().cpu().numpy()
-                x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-                if x.shape != (nfree,):
-                    raise ValueError('v must have shape (%d,)' % nfree)
-                d_v.assign(x)
+                d_v.assign(host_vector(np.reshape(x, -1), 'v', nfree))
                 handle.apply(values, d_v, d_y, hb.DEVICE)
                 hip.synchronize()
                 if like is not None:
@@ -1659,12 +1529,10 @@ class ConstraintCollocator(object):
                 return d_y.numpy()
 
             def apply_block(X):
-                like = X if hasattr(X, 'data_ptr') else None
+                like = X if on_device(X) else None
                 if like is not None:
                     X = X.detach().cpu().numpy()
-                if np.ndim(X) != 2 or np.shape(X)[0] != nfree:
-                    raise ValueError('X must have shape (%d, k)' % nfree)
-                X = column_major(X)
+                X = host_block(X, 'X', nfree)
                 k = X.shape[1]
                 d_X = hb.DeviceVector(X.T, self._device)
                 d_Y = hb.DeviceVector(np.zeros(k*nfree), self._device)
@@ -1677,7 +1545,9 @@ class ConstraintCollocator(object):
                     return torch.from_numpy(Y).to(like.device)
                 return Y
 
-        class HessianOperator(LinearOperator):
+        class HessianOperator(
+                tensor_operands('matvec', 'rmatvec', 'matmat'),
+                LinearOperator):
             """Symmetric; a torch CUDA vector, or a CUDA block of vectors of
             shape ``(num_free, k)``, is taken as it is (SciPy would convert
             it to an array) and answered with a CUDA tensor.  ``matmat`` is
@@ -1695,21 +1565,6 @@ class ConstraintCollocator(object):
                 return apply_block(X)
 
             _rmatmat = _matmat
-
-            def matmat(self, X):
-                if hasattr(X, 'data_ptr'):
-                    return apply_block(X)
-                return super().matmat(X)
-
-            def matvec(self, x):
-                if hasattr(x, 'data_ptr'):
-                    return apply(x)
-                return super().matvec(x)
-
-            def rmatvec(self, x):
-                if hasattr(x, 'data_ptr'):
-                    return apply(x)
-                return super().rmatvec(x)
         op = HessianOperator()
         op.values = values
         op.handle = handle
@@ -1736,29 +1591,16 @@ class ConstraintCollocator(object):
     # Hessian as CSR: unique lower triangle
     # ------------------------------------------------------------------
     def _ensure_hesscsr(self, objective=None):
-        """The CSR-Hessian handle (made on first use; one for the constraint
-        triplets alone, one per objective Hessian handle)."""
-        attr = '_hesscsr' if objective is None else '_hesscsr_objective'
-        if objective is not None and \
-                getattr(self, '_hesscsr_objective_of', None) is not objective:
-            old = getattr(self, attr, None)
-            if old is not None:
-                old.release()
-            setattr(self, attr, None)
-            self._hesscsr_objective_of = objective
-
-        def create(hip):
-            return hb.HipHessianCsr(
-                hip, self._hessmv_descriptor(objective)), {}
-        # (no program of its own: the compression is checked against
-        # scipy.sparse on the triplets by the test suite)
-        return self._ensure_derived(attr, create, lambda handle: None)
+        """The CSR-Hessian handle."""
+        return self._ensure_over_triplets('_hesscsr', hb.HipHessianCsr,
+                                          objective)
 
     @staticmethod
-    def _hessian_csr_structure_of(handle):
-        """``(indptr, indices)`` (int64) from ``handle``'s closed form."""
-        indptr = np.empty(handle._problem.num_free + 1, dtype=np.int64)
-        indices = np.empty(handle.nnz_unique, dtype=np.int64)
+    def _csr_structure_of(handle, rows, count):
+        """``(indptr, indices)`` (int64) of ``count`` entries in ``rows``
+        rows from ``handle``'s closed form."""
+        indptr = np.empty(rows + 1, dtype=np.int64)
+        indices = np.empty(count, dtype=np.int64)
         handle.structure(indptr, indices, hb.HOST)
         return indptr, indices
 
@@ -1774,7 +1616,9 @@ class ConstraintCollocator(object):
         # (what has no Hessian is refused before a device is asked for)
         self._build_hessian_program()
         self._ensure_hessian()
-        return self._hessian_csr_structure_of(self._ensure_hesscsr())
+        handle = self._ensure_hesscsr()
+        return self._csr_structure_of(handle, self.num_free,
+                                      handle.nnz_unique)
 
     def _hessian_csr_compress(self, handle):
         """``compress(values) -> data`` over ``handle``: host triplets in, a
@@ -1785,23 +1629,8 @@ class ConstraintCollocator(object):
         result = hb.pinned_empty(nu)
 
         def compress(values):
-            if hasattr(values, 'data_ptr'):
-                import torch
-                if tuple(values.shape) != (nnz,):
-                    raise ValueError('values have the wrong shape')
-                values = values.to(torch.float64).contiguous()
-                out = torch.empty(nu, dtype=torch.float64,
-                                  device=values.device)
-                torch.cuda.current_stream(values.device).synchronize()
-                handle.compress(values, out, hb.DEVICE)
-                hip.synchronize()
-                return out
-            values = np.ascontiguousarray(values, dtype=np.float64)
-            if values.shape != (nnz,):
-                raise ValueError('values must have shape ({},), got {}'
-                                 .format(nnz, values.shape))
-            handle.compress(values, result, hb.HOST)
-            return result
+            return call_vectors(handle.compress, ((values, 'values', nnz),),
+                                result, hip.synchronize)
         compress.result = result
         return compress
 
@@ -1829,29 +1658,20 @@ class ConstraintCollocator(object):
         own = {}
 
         def evaluate(free, lagrange):
-            if hasattr(free, 'data_ptr'):
+            point = ((free, 'free', nfree), (lagrange, 'lagrange', ncon))
+            if on_device(free):
                 import torch
-                if tuple(free.shape) != (nfree,) or \
-                        tuple(lagrange.shape) != (ncon,):
-                    raise ValueError('free / lagrange have the wrong shape')
-                free = free.to(torch.float64).contiguous()
-                lagrange = lagrange.to(device=free.device,
-                                       dtype=torch.float64).contiguous()
-                self._sync_known(hip, free.cpu().numpy()
-                                 if self._callable_known else None)
+                free, lagrange = device_vectors(point)
+                self._sync_free(free)
                 values = own.get('torch')
                 if values is None or values.device != free.device:
                     values = own['torch'] = torch.empty(
                         hess.nnz, dtype=torch.float64, device=free.device)
-                torch.cuda.current_stream(free.device).synchronize()
+                wait_for_torch(free.device)
                 hess.evaluate(free, lagrange, values, hb.DEVICE)
                 return compress(values)
-            free = self._host_free(free)
-            lagrange = np.ascontiguousarray(lagrange, dtype=np.float64)
-            if lagrange.shape != (ncon,):
-                raise ValueError('lagrange must have shape ({},), got {}'
-                                 .format(ncon, lagrange.shape))
-            self._sync_known(hip, free)
+            free, lagrange = host_vectors(point)
+            self._sync_free(free)
             if 'host' not in own:
                 own['host'] = tuple(
                     hb.DeviceVector(np.zeros(k), self._device)
@@ -1875,32 +1695,8 @@ class ConstraintCollocator(object):
             raise ValueError("%s needs jacobian_layout='csr'." % what)
 
     def _ensure_kktcsr(self, objective=None):
-        """The augmented-system handle (made on first use; one for the
-        constraint triplets alone, one per objective Hessian handle)."""
-        attr = '_kktcsr' if objective is None else '_kktcsr_objective'
-        if objective is not None and \
-                getattr(self, '_kktcsr_objective_of', None) is not objective:
-            old = getattr(self, attr, None)
-            if old is not None:
-                old.release()
-            setattr(self, attr, None)
-            self._kktcsr_objective_of = objective
-
-        def create(hip):
-            return hb.HipKktCsr(hip, self._hessmv_descriptor(objective)), {}
-        # (no program of its own: the assembly is checked against NumPy and
-        # scipy.sparse by the test suite)
-        return self._ensure_derived(attr, create, lambda handle: None)
-
-    @staticmethod
-    def _kkt_csr_structure_of(handle):
-        """``(indptr, indices)`` (int64) from ``handle``'s closed form."""
-        hip = handle._problem
-        indptr = np.empty(hip.num_free + hip.num_constraints + 1,
-                          dtype=np.int64)
-        indices = np.empty(handle.nnz_kkt, dtype=np.int64)
-        handle.structure(indptr, indices, hb.HOST)
-        return indptr, indices
+        """The augmented-system handle."""
+        return self._ensure_over_triplets('_kktcsr', hb.HipKktCsr, objective)
 
     def kkt_csr_structure(self):
         """``(indptr, indices)`` (int64) of the lower triangle of the
@@ -1919,7 +1715,9 @@ class ConstraintCollocator(object):
         self._require_csr_layout('kkt_csr_structure')
         self._build_hessian_program()
         self._ensure_hessian()
-        return self._kkt_csr_structure_of(self._ensure_kktcsr())
+        handle = self._ensure_kktcsr()
+        return self._csr_structure_of(
+            handle, self.num_free + self.num_constraints, handle.nnz_kkt)
 
     def _kkt_csr_assemble(self, handle):
         """``assemble(hess_values, jac_values, sigma=None, delta_w=0.0,
@@ -1933,43 +1731,11 @@ class ConstraintCollocator(object):
 
         def assemble(hess_values, jac_values, sigma=None, delta_w=0.0,
                      delta_c=0.0):
-            if hasattr(hess_values, 'data_ptr'):
-                import torch
-                if tuple(hess_values.shape) != (nh,) or \
-                        tuple(jac_values.shape) != (nj,) or \
-                        (sigma is not None and
-                         tuple(sigma.shape) != (nfree,)):
-                    raise ValueError('hess_values / jac_values / sigma have '
-                                     'the wrong shape')
-                dev = hess_values.device
-                hess_values = hess_values.to(torch.float64).contiguous()
-                jac_values = jac_values.to(
-                    device=dev, dtype=torch.float64).contiguous()
-                if sigma is not None:
-                    sigma = torch.as_tensor(sigma).to(
-                        device=dev, dtype=torch.float64).contiguous()
-                out = torch.empty(nk, dtype=torch.float64, device=dev)
-                torch.cuda.current_stream(dev).synchronize()
-                handle.assemble(hess_values, jac_values, sigma, delta_w,
-                                delta_c, out, hb.DEVICE)
-                hip.synchronize()
-                return out
-            hess_values = np.ascontiguousarray(hess_values, dtype=np.float64)
-            jac_values = np.ascontiguousarray(jac_values, dtype=np.float64)
-            if hess_values.shape != (nh,):
-                raise ValueError('hess_values must have shape ({},), got {}'
-                                 .format(nh, hess_values.shape))
-            if jac_values.shape != (nj,):
-                raise ValueError('jac_values must have shape ({},), got {}'
-                                 .format(nj, jac_values.shape))
-            if sigma is not None:
-                sigma = np.ascontiguousarray(sigma, dtype=np.float64)
-                if sigma.shape != (nfree,):
-                    raise ValueError('sigma must have shape ({},), got {}'
-                                     .format(nfree, sigma.shape))
-            handle.assemble(hess_values, jac_values, sigma, delta_w, delta_c,
-                            result, hb.HOST)
-            return result
+            return call_vectors(
+                handle.assemble,
+                ((hess_values, 'hess_values', nh),
+                 (jac_values, 'jac_values', nj), (sigma, 'sigma', nfree)),
+                result, hip.synchronize, scalars=(delta_w, delta_c))
         assemble.result = result
         return assemble
 
@@ -1984,18 +1750,14 @@ class ConstraintCollocator(object):
 
         def evaluate(free, lagrange, *extra, sigma=None, delta_w=0.0,
                      delta_c=0.0):
-            if hasattr(free, 'data_ptr'):
+            point = ((free, 'free', nfree), (lagrange, 'lagrange', ncon),
+                     (sigma, 'sigma', nfree))
+            if on_device(free):
                 import torch
-                if tuple(free.shape) != (nfree,) or \
-                        tuple(lagrange.shape) != (ncon,):
-                    raise ValueError('free / lagrange have the wrong shape')
-                if sigma is not None and tuple(sigma.shape) != (nfree,):
-                    raise ValueError('sigma has the wrong shape')
-                free = free.to(torch.float64).contiguous()
-                lagrange = lagrange.to(device=free.device,
-                                       dtype=torch.float64).contiguous()
-                self._sync_known(hip, free.cpu().numpy()
-                                 if self._callable_known else None)
+                if sigma is not None:       # (the assembly converts it)
+                    check_vector(*point[2])
+                free, lagrange = device_vectors(point[:2])
+                self._sync_free(free)
                 bufs = own.get('torch')
                 if bufs is None or bufs[0].device != free.device:
                     bufs = own['torch'] = tuple(
@@ -2003,21 +1765,12 @@ class ConstraintCollocator(object):
                                     device=free.device)
                         for k in (handle.nnz, hip.nnz))
                 values, jac = bufs
-                torch.cuda.current_stream(free.device).synchronize()
+                wait_for_torch(free.device)
                 hessian_into(free, lagrange, values, *extra)
                 hip.eval_jac(free, jac, hb.DEVICE)
                 return assemble(values, jac, sigma, delta_w, delta_c)
-            free = self._host_free(free)
-            lagrange = np.ascontiguousarray(lagrange, dtype=np.float64)
-            if lagrange.shape != (ncon,):
-                raise ValueError('lagrange must have shape ({},), got {}'
-                                 .format(ncon, lagrange.shape))
-            if sigma is not None:
-                sigma = np.ascontiguousarray(sigma, dtype=np.float64)
-                if sigma.shape != (nfree,):
-                    raise ValueError('sigma must have shape ({},), got {}'
-                                     .format(nfree, sigma.shape))
-            self._sync_known(hip, free)
+            free, lagrange, sigma = host_vectors(point)
+            self._sync_free(free)
             if 'host' not in own:
                 own['host'] = tuple(
                     hb.DeviceVector(np.zeros(k), self._device)
@@ -3529,11 +3282,15 @@ class ConstraintCollocator(object):
         self._multi_arg_con_jac_func = constraints_jacobian
 
     def _host_free(self, free):
-        free = np.ascontiguousarray(free, dtype=np.float64)
-        if free.shape != (self.num_free,):
-            raise ValueError('free must have shape ({},), got {}'.format(
-                self.num_free, free.shape))
-        return free
+        return host_vector(free, 'free', self.num_free)
+
+    def _sync_free(self, free):
+        """:meth:`_sync_known` for a converted ``free``, a host array or a
+        tensor (known trajectories given as functions of ``free`` are host
+        callables: they alone need a device ``free`` on the host)."""
+        if on_device(free):
+            free = free.cpu().numpy() if self._callable_known else None
+        self._sync_known(self._hip, free)
 
     # ------------------------------------------------------------------
     # public evaluation API (opty/direct_collocation.py:3003-3015, :2450)
@@ -3791,6 +3548,21 @@ class Problem(object):
                              'or of (problem, free).')
         return rows, cols, values
 
+    def _objective_hessian_of(self, obj_hessian):
+        """``(rows, cols, values, nargs, device_backed)`` of a checked
+        ``obj_hessian`` for this problem: the indices within ``num_free``,
+        ``nargs`` the number of arguments ``values`` takes (1 or 2), and
+        whether ``values`` is device-backed
+        (``create_objective_hessian_function``): it then applies
+        ``obj_factor`` itself and can fill a device buffer in place."""
+        rows, cols, values = obj_hessian
+        if np.any((rows < 0) | (rows >= self.num_free)):
+            raise ValueError('obj_hessian indices out of range.')
+        nargs = values.__code__.co_argcount - len(values.__defaults__ or ()) \
+            if hasattr(values, '__code__') else 1
+        return rows, cols, values, nargs, isinstance(
+            getattr(values, 'handle', None), hb.HipObjectiveHessian)
+
     def _install_hessian(self, obj_hessian):
         """Gives this instance the two callbacks cyipopt looks for --
         ``hessianstructure()`` and ``hessian(free, lagrange, obj_factor)``:
@@ -3798,29 +3570,21 @@ class Problem(object):
         triangle, summed duplicates), then the objective's.  Only an instance
         built with ``obj_hessian`` has them; without them IPOPT keeps its
         limited-memory quasi-Newton default."""
-        rows, cols, values = obj_hessian
-        if np.any((rows < 0) | (rows >= self.num_free)):
-            raise ValueError('obj_hessian indices out of range.')
+        rows, cols, values, nargs, device_backed = \
+            self._objective_hessian_of(obj_hessian)
         col = self.collocator
         con_hess = col.generate_hessian_function()
         crows, ccols = col.hessian_indices()
         structure = (np.concatenate((crows, rows)),
                      np.concatenate((ccols, cols)))
-        nargs = values.__code__.co_argcount - len(values.__defaults__ or ()) \
-            if hasattr(values, '__code__') else 1
         num_con = len(crows)
 
         def hessianstructure():
             return structure
 
-        # a device-backed ``values`` (``create_objective_hessian_function``)
-        # applies ``obj_factor`` itself and can fill a device buffer in place
-        on_device = isinstance(getattr(values, 'handle', None),
-                               hb.HipObjectiveHessian)
-
         def hessian(free, lagrange, obj_factor):
-            if hasattr(free, 'data_ptr'):
-                if not on_device:
+            if on_device(free):
+                if not device_backed:
                     raise TypeError(
                         'Problem.hessian with torch CUDA tensors needs an '
                         'obj_hessian whose values have a device handle '
@@ -3836,7 +3600,7 @@ class Problem(object):
                 return out
             out = np.empty(num_con + len(rows))
             out[:num_con] = con_hess(free, lagrange)
-            if on_device:
+            if device_backed:
                 values(free, obj_factor, out[num_con:])
                 return out
             v = values(self, free) if nargs == 2 else values(free)
@@ -3847,7 +3611,7 @@ class Problem(object):
 
         def objective_handle(method):
             """The device handle of ``values``, of this problem's sizes."""
-            if not on_device:
+            if not device_backed:
                 raise TypeError(
                     'Problem.%s needs an obj_hessian whose '
                     'values have a device handle (values.handle: opty_amd.'
@@ -3875,12 +3639,10 @@ class Problem(object):
             (``opty_amd.create_objective_hessian_function``)."""
             objective = objective_handle('hessian_operator')
             handle = col._ensure_hessmv(objective)
-            if hasattr(free, 'data_ptr'):
-                vals = hessian(free, lagrange, obj_factor)
-            else:
-                vals = hessian(np.ascontiguousarray(free, dtype=float),
-                               lagrange, obj_factor)
-            return col._hessian_operator(handle, vals)
+            if not on_device(free):
+                free = col._host_free(free)
+            return col._hessian_operator(
+                handle, hessian(free, lagrange, obj_factor))
         self.hessian_operator = hessian_operator
 
         def hessian_csr_structure():
@@ -3892,7 +3654,8 @@ class Problem(object):
             device-backed ``obj_hessian``."""
             handle = col._ensure_hesscsr(
                 objective_handle('hessian_csr_structure'))
-            return col._hessian_csr_structure_of(handle)
+            return col._csr_structure_of(handle, col.num_free,
+                                         handle.nnz_unique)
 
         csr = {}
 
@@ -3907,8 +3670,8 @@ class Problem(object):
             if csr.get('handle') is not handle:
                 csr.update(handle=handle,
                            compress=col._hessian_csr_compress(handle))
-            if not hasattr(free, 'data_ptr'):
-                free = np.ascontiguousarray(free, dtype=float)
+            if not on_device(free):
+                free = col._host_free(free)
             return csr['compress'](hessian(free, lagrange, obj_factor))
         self.hessian_csr_structure = hessian_csr_structure
         self.hessian_csr = hessian_csr
@@ -3923,7 +3686,8 @@ class Problem(object):
             ``jacobian_layout='csr'`` and a device-backed ``obj_hessian``."""
             col._require_csr_layout('Problem.kkt_csr_structure')
             handle = col._ensure_kktcsr(objective_handle('kkt_csr_structure'))
-            return col._kkt_csr_structure_of(handle)
+            return col._csr_structure_of(
+                handle, col.num_free + col.num_constraints, handle.nnz_kkt)
 
         kkt = {}
 
@@ -3951,19 +3715,19 @@ class Problem(object):
                 kkt.update(handle=handle, function=col._kkt_csr_function(
                     handle, hessian_into))
             function = kkt['function']
-            if hasattr(free, 'data_ptr'):
+            if on_device(free):
                 return function(free, lagrange, obj_factor, sigma=sigma,
                                 delta_w=delta_w, delta_c=delta_c)
             import torch
             device = torch.device('cuda', col._device)
-            free = col._host_free(free)
-            lagrange = np.ascontiguousarray(lagrange, dtype=np.float64)
-            if sigma is not None:
-                sigma = torch.from_numpy(np.ascontiguousarray(
-                    sigma, dtype=np.float64)).to(device)
-            out = function(torch.from_numpy(free).to(device),
-                           torch.from_numpy(lagrange).to(device), obj_factor,
-                           sigma=sigma, delta_w=delta_w, delta_c=delta_c)
+            free, lagrange, sigma = (
+                x if x is None else torch.from_numpy(x).to(device)
+                for x in host_vectors((
+                    (free, 'free', col.num_free),
+                    (lagrange, 'lagrange', col.num_constraints),
+                    (sigma, 'sigma', col.num_free))))
+            out = function(free, lagrange, obj_factor, sigma=sigma,
+                           delta_w=delta_w, delta_c=delta_c)
             result = function.assemble.result
             result[:] = out.cpu().numpy()
             return result
@@ -4252,9 +4016,8 @@ class ShardedProblem(Problem):
         section served by all ranks.  Every rank gets here (the size of the
         shared vector is agreed without communication); only the root holds
         the structure and ever calls ``values``."""
-        rows, cols, values = obj_hessian
-        if np.any((rows < 0) | (rows >= self.num_free)):
-            raise ValueError('obj_hessian indices out of range.')
+        rows, cols, values, nargs, device_backed = \
+            self._objective_hessian_of(obj_hessian)
         cb, col = self.callbacks, self.collocator
         cb.hessian_extra = len(rows)
         if not cb.is_root:
@@ -4266,27 +4029,23 @@ class ShardedProblem(Problem):
         assert len(crows) == num_con
         structure = (np.concatenate((crows, rows)),
                      np.concatenate((ccols, cols)))
-        nargs = values.__code__.co_argcount - len(values.__defaults__ or ()) \
-            if hasattr(values, '__code__') else 1
-        on_device = isinstance(getattr(values, 'handle', None),
-                               hb.HipObjectiveHessian)
         obj_dev = []
 
         def hessianstructure():
             return structure
 
         def hessian(free, lagrange, obj_factor):
-            if hasattr(free, 'data_ptr') or hasattr(lagrange, 'data_ptr'):
+            if on_device(free) or on_device(lagrange):
                 raise TypeError(
                     'ShardedProblem.hessian takes host arrays only: the '
                     'result is assembled in a host vector shared by the '
                     'ranks, not in one GPU\'s memory; pass NumPy arrays '
                     '(free.cpu().numpy()).')
-            free = np.ascontiguousarray(free, dtype=np.float64)
+            free = col._host_free(free)
             out = cb.hessian(free, lagrange)
             if not len(rows):
                 return out
-            if on_device:
+            if device_backed:
                 # the root's own GPU, into the (page-locked) shared vector
                 # behind the constraint section
                 import torch

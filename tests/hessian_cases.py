@@ -2,6 +2,7 @@
 Hessian program, the small problems whose modules cover every flush variant
 of ``codegen/emit_hessian.py``, the flush calls of an emitted source, and the
 code objects that ``__graft_entry__.build`` prebuilds for them."""
+import functools
 import re
 
 import numpy as np
@@ -42,6 +43,10 @@ BLOCK_EDGE_CASES = ([('A', m) for m in EDGES] + [('E', m) for m in EDGES] +
 #: and a known trajectory (every kernel of both modules runs)
 LIFECYCLE_CASES = (('A', 65), ('C', 65))
 
+#: (label, N - 1) of the checks of how the Python surface takes its arguments
+#: (:func:`surface_case`): five nodes, without and with instance constraints
+SURFACE_CASES = (('A', 4), ('C', 4))
+
 #: the code generator's default (``ConstraintCollocator._HESS_STRIP_OPS``)
 DEFAULT_VARIANT = (1500, False, 1)
 #: (label, (strip budget, forget, fast_trig)) of the emission paths that no
@@ -76,6 +81,36 @@ def inputs(seed, col):
     if col._variable_duration:
         free[-1] = 0.02
     return free, rng.uniform(-1.0, 1.0, col.num_constraints)
+
+
+@functools.lru_cache(maxsize=None)
+def surface_case(label):
+    """``(collocator, free, lagrange)`` of ``SURFACE_CASES`` -- in the CSR
+    layout, which the augmented system needs and every other function takes
+    --, one for all the test files: its handles are made once.  Nobody
+    writes to the inputs."""
+    col = collocator(label, dict(SURFACE_CASES)[label], jacobian_layout='csr')
+    free, lam = inputs(17, col)
+    free.flags.writeable = lam.flags.writeable = False
+    return col, free, lam
+
+
+def odd(a):
+    """``(tensor, array)``: the values of ``a`` rounded to float32 as a CUDA
+    tensor that is neither float64 nor contiguous (every other element of a
+    float32 buffer; a two-dimensional ``a``: every other column), and as the
+    float64 host array a function should make of it."""
+    import torch
+    a32 = np.asarray(a).astype(np.float32)
+    wide = torch.from_numpy(np.repeat(a32, 2, axis=-1)).cuda()
+    return wide[..., ::2], a32.astype(np.float64)
+
+
+def bits(a):
+    """The bit patterns of ``a`` (an array or a tensor of doubles)."""
+    if hasattr(a, 'cpu'):
+        a = a.cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def interpreted(col, free, lam, nodes=None):
@@ -162,6 +197,11 @@ def prebuild_jobs():
             forced_module(collocator(label, 65), variant)
         for label, ncn in LIFECYCLE_CASES:
             collocator(label, ncn)._build_jacprod_code_object()
+        for label, ncn in SURFACE_CASES:
+            col = collocator(label, ncn, jacobian_layout='csr')
+            col.prebuild()
+            col._build_jacprod_code_object()
+            col._build_jacprod_block_code_object()
 
     def named(name):
         col = opty_amd.ConstraintCollocator(**problems.build(name))

@@ -362,3 +362,40 @@ def test_direct_kkt_step_of_the_example():
     print('|K (z_direct - z_minres)| = %.3e, minres residual %.3e'
           % (apart, history[-1]))
     assert apart <= residual + history[-1]*(1 + 1e-12)
+
+
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_functions_take_their_arguments(label):
+    """Host arrays: ``hcsr`` and ``hcsr.compress`` answer from one persistent
+    buffer, ``compress.result``.  Tensors that are neither float64 nor
+    contiguous: converted on the device, a new tensor per call with the bits
+    of the host path."""
+    import torch
+    col, free, lam = hc.surface_case(label)
+    hcsr = col.generate_hessian_csr_function()
+    first = hcsr(free, lam)
+    assert first is hcsr.compress.result
+    assert hcsr(free.tolist(), lam.astype(np.float32)) is first
+    values = np.array(col.generate_hessian_function()(free, lam))
+    assert hcsr.compress(values.tolist()) is first
+    dfree, free32 = hc.odd(free)
+    dlam, lam32 = hc.odd(lam)
+    assert dlam.dtype == torch.float32 and not dlam.is_contiguous()
+    want = hcsr(free32, lam32).copy()
+    out, again = hcsr(dfree, dlam), hcsr(dfree, dlam)
+    assert out.is_cuda and out.dtype == torch.float64
+    assert out.data_ptr() != again.data_ptr()
+    assert np.array_equal(cc.bits(out.cpu().numpy()), cc.bits(want))
+    assert np.array_equal(cc.bits(again.cpu().numpy()), cc.bits(want))
+    dvalues, values32 = hc.odd(values)
+    want = hcsr.compress(values32).copy()
+    out = hcsr.compress(dvalues)
+    assert out.is_cuda and out.dtype == torch.float64
+    assert np.array_equal(cc.bits(out.cpu().numpy()), cc.bits(want))
+    with pytest.raises(ValueError, match=r'values must have shape \(%d,\), '
+                       r'got \(%d,\)' % (len(values), len(values) - 1)):
+        hcsr.compress(values[1:])
+    with pytest.raises(ValueError, match='values must have shape'):
+        hcsr.compress(dvalues[1:])
+    with pytest.raises(ValueError, match='lagrange must have shape'):
+        hcsr(dfree, dlam[1:])

@@ -171,6 +171,36 @@ def test_problem_with_objective_hessian():
     assert not hasattr(plain, 'hessianstructure')
 
 
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_function_takes_its_arguments(label):
+    """Host arrays: one persistent buffer, whatever the arrays were made of.
+    Tensors that are neither float64 nor contiguous: converted on the device,
+    a new tensor per call with the bits of the host path."""
+    import torch
+    import hessian_cases as hc
+    col, free, lam = hc.surface_case(label)
+    hess = col.generate_hessian_function()
+    first = hess(free, lam)
+    assert hess(free.tolist(), lam.astype(np.float32)) is first
+    dfree, free32 = hc.odd(free)
+    dlam, lam32 = hc.odd(lam)
+    assert dfree.dtype == torch.float32 and not dfree.is_contiguous()
+    want = hess(free32, lam32).copy()
+    out, again = hess(dfree, dlam), hess(dfree, dlam)
+    assert out.is_cuda and out.dtype == torch.float64
+    assert tuple(out.shape) == want.shape
+    assert out.data_ptr() != again.data_ptr()
+    assert np.array_equal(hc.bits(out), hc.bits(want))
+    assert np.array_equal(hc.bits(again), hc.bits(want))
+    with pytest.raises(ValueError, match=r'lagrange must have shape \(%d,\), '
+                       r'got \(%d,\)' % (len(lam), len(lam) - 1)):
+        hess(free, lam[1:])
+    with pytest.raises(ValueError, match='free must have shape'):
+        hess(dfree[1:], dlam)
+    with pytest.raises(ValueError, match='lagrange must have shape'):
+        hess(dfree, dlam[1:])
+
+
 def test_exact_hessian_example_converges(capsys):
     from examples import vyasarayani_exact_hessian, vyasarayani_scipy
     p_hat, res = vyasarayani_exact_hessian.main()

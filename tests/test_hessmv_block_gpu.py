@@ -400,3 +400,37 @@ def test_extreme_eigenvalues_of_the_example():
     assert np.all(np.abs(smallest - w[:ex.BLOCK]) <= tol)
     assert np.all(np.abs(largest - w[-ex.BLOCK:]) <= tol)
     assert products > 2
+
+
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_block_product_takes_its_arguments(label):
+    """Host blocks: a new column-major array per call.  A tensor block that
+    is neither float64 nor contiguous: its columns are gathered on the device
+    and the result, the bits of the host path, is the transposed view of a
+    ``(k, n)`` buffer; no column, no launch."""
+    import torch
+    col, free, lam = hc.surface_case(label)
+    hmm = col.generate_hessian_block_product_function()
+    nfree, k = col.num_free, 2*hmm.handle.block_width + 1
+    values = np.array(col.generate_hessian_function()(free, lam))
+    V = np.random.default_rng(29).uniform(-1.0, 1.0, (nfree, k))
+    dvalues, values32 = hc.odd(values)
+    dV, V32 = hc.odd(V)
+    assert dV.dtype == torch.float32 and not dV.is_contiguous()
+    want = hmm(values32, V32.tolist())
+    assert want.flags.f_contiguous and hmm(values32, V32) is not want
+    out = hmm(dvalues, dV)
+    assert out.is_cuda and out.dtype == torch.float64
+    assert tuple(out.shape) == (nfree, k) and out.t().is_contiguous()
+    assert np.array_equal(hc.bits(out), hc.bits(want))
+    empty = hmm(dvalues, dV[:, :0])
+    assert empty.is_cuda and tuple(empty.shape) == (nfree, 0)
+    one = hmm(dvalues, dV[:, 1:2])
+    assert np.array_equal(hc.bits(one)[:, 0], hc.bits(want[:, 1]))
+    with pytest.raises(ValueError, match=r'V must have shape \(%d, k\), got '
+                       r'\(%d, %d\)' % (nfree, nfree - 1, k)):
+        hmm(values, V[1:])
+    with pytest.raises(ValueError, match='V must have shape'):
+        hmm(dvalues, dV[1:])
+    with pytest.raises(ValueError, match='values must have shape'):
+        hmm(dvalues[1:], dV)

@@ -405,3 +405,33 @@ def test_kkt_operator_of_the_example():
              np.r_[hcols, jcols], np.r_[hvals, jvals], z)
     step, history = kkt_minres.main(20, maxiter=5, verbose=False)
     assert step.shape == (n + m,) and len(history) >= 1
+
+
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_product_takes_its_arguments(label):
+    """Host arrays: one persistent buffer.  Tensors that are neither float64
+    nor contiguous: converted on the device, a new tensor per call with the
+    bits of the host path."""
+    import torch
+    col, free, lam = hc.surface_case(label)
+    hmv = col.generate_hessian_product_function()
+    values = np.array(col.generate_hessian_function()(free, lam))
+    v = free[::-1]
+    first = hmv(values, v)
+    assert hmv(values.tolist(), v.astype(np.float32)) is first
+    dvalues, values32 = hc.odd(values)
+    dv, v32 = hc.odd(v)
+    assert dv.dtype == torch.float32 and not dv.is_contiguous()
+    want = hmv(values32, v32).copy()
+    out, again = hmv(dvalues, dv), hmv(dvalues, dv)
+    assert out.is_cuda and out.dtype == torch.float64
+    assert out.data_ptr() != again.data_ptr()
+    assert np.array_equal(hc.bits(out), hc.bits(want))
+    assert np.array_equal(hc.bits(again), hc.bits(want))
+    with pytest.raises(ValueError, match=r'v must have shape \(%d,\), got '
+                       r'\(%d,\)' % (len(v), len(v) - 1)):
+        hmv(values, v[1:])
+    with pytest.raises(ValueError, match='values must have shape'):
+        hmv(dvalues[1:], dv)
+    with pytest.raises(ValueError, match='v must have shape'):
+        hmv(dvalues, dv[1:])

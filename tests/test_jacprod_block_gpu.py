@@ -425,3 +425,47 @@ def test_abi_destroy_null(abi):
     extra = _create(abi)
     assert extra.width == abi['col']._jacprod_block_meta['width']
     extra.release()
+
+
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_block_functions_take_their_arguments(label):
+    """Host blocks: a new column-major array per call.  A tensor block that
+    is neither float64 nor contiguous: its columns are gathered on the device
+    and the result, the bits of the host path, is the transposed view of a
+    ``(k, n)`` buffer; no column, no launch; one column is the single
+    product."""
+    import torch
+    import hessian_cases as hc
+    col, free, lam = hc.surface_case(label)
+    jmm, jtmm = _functions(col)
+    singles = (col.generate_jvp_function(), col.generate_vjp_function())
+    dfree, free32 = hc.odd(free)
+    rng = np.random.default_rng(23)
+    for f, single, nin, nout in (
+            (jmm, singles[0], col.num_free, col.num_constraints),
+            (jtmm, singles[1], col.num_constraints, col.num_free)):
+        k = 2*f.width + 1
+        X = rng.uniform(-1.0, 1.0, (nin, k))
+        dX, X32 = hc.odd(X)
+        assert dX.dtype == torch.float32 and not dX.is_contiguous()
+        want = f(free32, X32.tolist())
+        assert want.flags.f_contiguous and f(free32, X32) is not want
+        out = f(dfree, dX)
+        assert out.is_cuda and out.dtype == torch.float64
+        assert tuple(out.shape) == (nout, k) and out.t().is_contiguous()
+        assert np.array_equal(_bits(out.cpu().numpy()), _bits(want))
+        empty = f(dfree, dX[:, :0])
+        assert empty.is_cuda and tuple(empty.shape) == (nout, 0)
+        assert f(free32, X32[:, :0]).shape == (nout, 0)
+        one = f(dfree, dX[:, 1:2])
+        assert tuple(one.shape) == (nout, 1)
+        assert np.array_equal(_bits(one.cpu().numpy()[:, 0]),
+                              _bits(single(free32, X32[:, 1])))
+        with pytest.raises(ValueError, match=r'must have shape \(%d, k\), '
+                           r'got \(%d, %d\)' % (nin, nin - 1, k)):
+            f(free32, X32[1:])
+        with pytest.raises(ValueError, match=r'must have shape \(%d, k\)'
+                           % nin):
+            f(dfree, dX[1:])
+        with pytest.raises(ValueError, match='free must have shape'):
+            f(dfree[1:], dX)

@@ -267,3 +267,33 @@ def test_c_abi_errors():
     assert lib.opty_hip_jacprod_destroy(None) == 0
     # the handle still works
     assert np.all(np.isfinite(jvp(free, v)))
+
+
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_functions_take_their_arguments(label):
+    """Host arrays: one persistent buffer per function.  Tensors that are
+    neither float64 nor contiguous: converted on the device, a new tensor per
+    call with the bits of the host path."""
+    import torch
+    import hessian_cases as hc
+    col, free, lam = hc.surface_case(label)
+    dfree, free32 = hc.odd(free)
+    for f, name, x in ((col.generate_jvp_function(), 'v', free[::-1]),
+                       (col.generate_vjp_function(), 'w', lam)):
+        first = f(free, x)
+        assert f(free.tolist(), x.astype(np.float32)) is first
+        dx, x32 = hc.odd(x)
+        assert dx.dtype == torch.float32 and not dx.is_contiguous()
+        want = f(free32, x32).copy()
+        out, again = f(dfree, dx), f(dfree, dx)
+        assert out.is_cuda and out.dtype == torch.float64
+        assert out.data_ptr() != again.data_ptr()
+        assert np.array_equal(hc.bits(out), hc.bits(want))
+        assert np.array_equal(hc.bits(again), hc.bits(want))
+        with pytest.raises(ValueError, match=r'%s must have shape \(%d,\), '
+                           r'got \(%d,\)' % (name, len(x), len(x) - 1)):
+            f(free, x[1:])
+        with pytest.raises(ValueError, match='%s must have shape' % name):
+            f(dfree, dx[1:])
+        with pytest.raises(ValueError, match='free must have shape'):
+            f(dfree[1:], dx)

@@ -364,3 +364,50 @@ def test_handle_lifetime():
     assert handle._h is None
     with pytest.raises(hb.HipBackendError, match='closed'):
         kkt.assemble(got['hvals'], got['jvals'])
+
+
+@pytest.mark.parametrize('label', ['A', 'C'])
+def test_how_the_functions_take_their_arguments(label):
+    """Host arrays: ``kkt`` and ``kkt.assemble`` answer from one persistent
+    buffer, ``assemble.result``.  Tensors that are neither float64 nor
+    contiguous, ``sigma`` among them: converted on the device, a new tensor
+    per call with the bits of the host path."""
+    import torch
+    col, free, lam = hc.surface_case(label)
+    kkt = col.generate_kkt_csr_function()
+    sigma = np.random.default_rng(31).uniform(0.0, 1.0, col.num_free)
+    first = kkt(free, lam)
+    assert first is kkt.assemble.result
+    assert kkt(free.tolist(), lam.astype(np.float32),
+               sigma=sigma.tolist()) is first
+    hvals = np.array(col.generate_hessian_function()(free, lam))
+    jvals = np.array(col.generate_jacobian_function()(free))
+    assert kkt.assemble(hvals.tolist(), jvals.tolist()) is first
+    dfree, free32 = hc.odd(free)
+    dlam, lam32 = hc.odd(lam)
+    dsigma, sigma32 = hc.odd(sigma)
+    assert dsigma.dtype == torch.float32 and not dsigma.is_contiguous()
+    for given, host in ((dict(), dict()),
+                        (dict(sigma=dsigma, delta_w=1e-4, delta_c=1e-8),
+                         dict(sigma=sigma32, delta_w=1e-4, delta_c=1e-8))):
+        want = kkt(free32, lam32, **host).copy()
+        out, again = kkt(dfree, dlam, **given), kkt(dfree, dlam, **given)
+        assert out.is_cuda and out.dtype == torch.float64
+        assert out.data_ptr() != again.data_ptr()
+        assert np.array_equal(kc.bits(out.cpu().numpy()), kc.bits(want))
+        assert np.array_equal(kc.bits(again.cpu().numpy()), kc.bits(want))
+    dh, h32 = hc.odd(hvals)
+    dj, j32 = hc.odd(jvals)
+    want = kkt.assemble(h32, j32, sigma32, 1e-4).copy()
+    out = kkt.assemble(dh, dj, dsigma, 1e-4)
+    assert out.is_cuda and out.dtype == torch.float64
+    assert np.array_equal(kc.bits(out.cpu().numpy()), kc.bits(want))
+    with pytest.raises(ValueError, match=r'sigma must have shape \(%d,\), '
+                       r'got \(%d,\)' % (len(sigma), len(sigma) - 1)):
+        kkt(free, lam, sigma=sigma[1:])
+    with pytest.raises(ValueError, match='sigma must have shape'):
+        kkt(dfree, dlam, sigma=dsigma[1:])
+    with pytest.raises(ValueError, match='jac_values must have shape'):
+        kkt.assemble(dh, dj[1:])
+    with pytest.raises(ValueError, match='lagrange must have shape'):
+        kkt(dfree, dlam[1:])
