@@ -99,10 +99,13 @@ class Reference(object):
     """The pattern of ``K`` from matrices of ones -- nothing cancels, every
     diagonal is there -- and what maps values to it, by SciPy alone."""
 
-    def __init__(self, col):
+    def __init__(self, col, hrows=None, hcols=None):
+        """``hrows, hcols``: the Hessian's triplet indices where they are not
+        the problem's own (a handle made from a synthetic descriptor)."""
         import scipy.sparse as sp
         self.n, self.m = n, m = col.num_free, col.num_constraints
-        hrows, hcols = col.hessian_indices_closed_form()
+        if hrows is None:
+            hrows, hcols = col.hessian_indices_closed_form()
         self.hrows, self.hcols = hrows, hcols
         Hpat = sp.coo_matrix((np.ones(len(hrows)), (hrows, hcols)),
                              shape=(n, n)).tocsr()

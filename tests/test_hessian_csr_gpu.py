@@ -67,17 +67,21 @@ def _device_compress(hip, handle, values, what):
     return buf.check(what)
 
 
-def _hold(what, hip, handle, N, nrows, ntail, desc, rows, cols, values):
+def _hold(what, hip, handle, N, nrows, ntail, desc, rows, cols, values,
+          ref=None):
     """The handle's structure (both memory kinds) against the host
     statement's and SciPy's; its data from device memory, from host memory
     and a second time: right, all written, the same bits.  Returns ``(data,
-    reference)``."""
+    reference)``.  ``ref``: the reference where it is not that of the
+    triplets alone (a handle with every diagonal: ``desc`` then says
+    ``with_diagonal`` to the host statement)."""
     import torch
     from opty_amd import hip_backend as hb
     from opty_amd.codegen.program import hessian_csr_structure
     num_free = nrows*N + ntail
     assert handle.nnz == len(values) == len(rows)
-    ref = cc.Reference(num_free, nrows*N, N - 1, rows, cols, values)
+    if ref is None:
+        ref = cc.Reference(num_free, nrows*N, N - 1, rows, cols, values)
     assert handle.nnz_unique == len(ref.count)
     indptr = np.empty(num_free + 1, dtype=np.int64)
     indices = np.empty(handle.nnz_unique, dtype=np.int64)

@@ -42,14 +42,16 @@ def _device_assemble(hip, handle, hvals, jvals, sigma, dw, dc, what):
     return buf.check(what)
 
 
-def _case(label, ncn, prune, seed=91):
-    """One collocator through every check of the block-edge cases; returns
-    what the other tests go on with."""
+def _case(label, ncn, prune, seed=91, col=None):
+    """One collocator (``col``: a problem that is not on the list) through
+    every check of the block-edge cases; returns what the other tests go on
+    with."""
     import torch
     from opty_amd import hip_backend as hb
     from opty_amd.codegen.program import kkt_csr_structure
     what = '%s N-1=%d prune=%s' % (label, ncn, prune)
-    col = kc.collocator(label, ncn, prune)
+    if col is None:
+        col = kc.collocator(label, ncn, prune)
     kkt = col.generate_kkt_csr_function()
     handle = kkt.handle
     ref = kc.Reference(col)
