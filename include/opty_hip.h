@@ -183,7 +183,7 @@ typedef struct opty_hip_desc {
  * opty_hip_eval_hess_instance / opty_hip_hessian_indices_range, and then the
  * opty_hip_hesscsr_* entry points, and then
  * opty_hip_hesscsr_create_with_diagonal and the opty_hip_kktcsr_* entry
- * points), and
+ * points, and then opty_hip_hessmv_apply_shard), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -1013,6 +1013,48 @@ int opty_hip_hessmv_apply_block(opty_hip_hessmv *h, const double *values,
                                 int32_t ncols, int32_t mem);
 /* columns one pass takes (1 .. 4), fixed at create from the LDS the side table needs */
 int32_t opty_hip_hessmv_block_width(const opty_hip_hessmv *h);
+
+/* ---- Hessian operator over a node window (shards that stay in device memory) --
+ * What opty_hip_jacprod_vjp_shard is to J^T w: the share of y = H v of the
+ * constraint nodes [node_begin, node_end), from the GLOBAL v (num_free doubles)
+ * and the values of those nodes where opty_hip_eval_hess_shard left them.  The
+ * handle is one of the constraint section alone (E == 0 and T == 0: the
+ * objective section is not node-sharded).
+ *   values_shard : values_shard[(i - i_first)*PH + e], i_first = node_begin -
+ *                  (node_begin > 0): entry p of a trajectory row needs node p - 1
+ *                  too, so a window that does not start the problem holds one
+ *                  (halo) node in front; 8-byte alignment is enough
+ *   inst_values  : the nnz_inst instance values (opty_hip_eval_hess_instance)
+ *   out          : the window OWNS the time nodes p in [node_begin, pend), pend =
+ *                  node_end + (node_end == N - 1): out[R*out_stride + p -
+ *                  node_begin] is entry R*N + p of y, out_stride >= pend -
+ *                  node_begin; the instance triplets' sides at owned entries
+ *                  included, in stored order
+ *   tail_part    : r + s doubles by tail offset: the window's share of the
+ *                  node-invariant entries -- the sum over its nodes, block
+ *                  partials in block order; an entry without a side is 0.0 --
+ *                  and, for the ONE call of a partition with tail_owner != 0, on
+ *                  top of it the instance triplets' tail sides.  The entries
+ *                  themselves are the sum of the windows' shares.
+ * Contract: every entry of `out` has the bits of opty_hip_hessmv_apply on the
+ * same handle and the whole problem's values, for every partition of the nodes;
+ * tail_part has the same bits from call to call, and for the window [0, N - 1)
+ * with tail_owner the bits of the whole product's tail; for other partitions it
+ * is the same sum cut differently.  Nothing but the owned entries of `out` and
+ * tail_part is written.  Device pointers only; enqueued on the problem's
+ * stream, not synchronised.  Refused before anything is enqueued: null pointers
+ * (inst_values may be NULL when nnz_inst == 0, tail_part when r + s == 0), a
+ * window outside [0, N - 1] or with node_begin > node_end, an out_stride below
+ * the owned width, a range of `out` that overlaps v or values_shard, a handle
+ * with an objective section.  An empty window zero-fills tail_part and -- when
+ * it owns the tail and the handle has instance triplets -- runs opty_hessmv_fin
+ * alone; otherwise it launches nothing. */
+int opty_hip_hessmv_apply_shard(opty_hip_hessmv *h,
+                                const double *values_shard,
+                                const double *inst_values, const double *v,
+                                double *out, int64_t out_stride,
+                                double *tail_part, int64_t node_begin,
+                                int64_t node_end, int32_t tail_owner);
 
 /* ---- Hessian as CSR: unique lower triangle, duplicates summed ------------------
  * The triplets of the Hessian of the Lagrangian -- `values` laid out as for the

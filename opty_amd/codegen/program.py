@@ -680,6 +680,88 @@ def assemble_hessmv(N, num_rows, num_tail, values, v, pattern, inst_rows=(),
     return y
 
 
+#: nodes a block of ``opty_hessmv`` advances by (64 lanes, one repeated node)
+HESSMV_STRIDE = 63
+
+
+def hessmv_window_owned(N, a, b):
+    """``(lo, hi)``: the time nodes whose trajectory entries of ``H v`` the
+    window ``[a, b)`` of the ``N - 1`` constraint nodes owns -- its nodes' and,
+    for a non-empty window that ends the problem, node ``N - 1``."""
+    a, b = int(a), int(b)
+    return a, b + (1 if a < b == int(N) - 1 else 0)
+
+
+def hessmv_window_blocks(N, a, b):
+    """Blocks of ``opty_hessmv`` over the window ``[a, b)``: block 0 of a
+    window that starts the problem stores 64 time nodes, every other block 63
+    (its lane 0 is the halo node or repeats a node); at least one for a
+    non-empty window, none for an empty one.  ``[0, N - 1)`` gives the
+    whole-problem launch, ``ceil((N - 1)/63)``."""
+    lo, hi = hessmv_window_owned(N, a, b)
+    if int(b) <= int(a):
+        return 0
+    todo = hi - lo - (1 if lo == 0 else 0)
+    return max(1, -(-todo//HESSMV_STRIDE))
+
+
+def assemble_hessmv_window(N, num_rows, num_tail, values_shard, inst_values,
+                           v, pattern, a, b, tail_owner, inst_rows=(),
+                           inst_cols=()):
+    """One window of :func:`assemble_hessmv` over the constraint section: the
+    host statement of ``opty_hip_hessmv_apply_shard``.  ``values_shard`` holds
+    the nodes ``[a - (a > 0), b)`` (one halo node in front of a window that
+    does not start the problem), ``inst_values`` the instance entries, ``v``
+    is the GLOBAL vector.  Returns ``(block, tail_part)``: ``block[R, p - a]``
+    is entry ``R*N + p`` of ``H v`` for the owned time nodes
+    (:func:`hessmv_window_owned`), with the operations of
+    :func:`assemble_hessmv` in its order -- the same bits --; ``tail_part``
+    (``num_tail`` doubles) the sum over the window's own nodes per tail
+    entry and, for the ``tail_owner``, the instance triplets' tail sides on
+    top.  An instance side at a trajectory entry goes to the window that owns
+    the entry; every other side is skipped."""
+    import numpy as np
+    N, a, b = int(N), int(a), int(b)
+    sides, ntraj, entries, _ = hessian_side_table(pattern)
+    PH = len(entries)
+    first = a - (1 if a > 0 else 0) if b > a else a
+    nodes = np.arange(first, b)
+    lo, hi = hessmv_window_owned(N, a, b)
+    v = np.asarray(v, dtype=float)
+    tail = num_rows*N
+    assert v.shape == (tail + num_tail,)
+    node = np.asarray(values_shard, dtype=float)[:len(nodes)*PH].reshape(
+        len(nodes), PH)
+    at = [np.broadcast_to(v[row*N + nodes + off] if row >= 0
+                          else v[tail + off], nodes.shape)
+          for row, off in sides]
+    S = np.zeros((len(sides), len(nodes)))
+    for e, (sa, sb) in enumerate(entries):
+        S[sa] += node[:, e]*at[sb]
+        if sa != sb:
+            S[sb] += node[:, e]*at[sa]
+    block = np.zeros((num_rows, hi - lo))
+    tail_part = np.zeros(num_tail)
+    for k, (row, off) in enumerate(sides):
+        if row >= 0:
+            p = nodes + off
+            keep = (p >= lo) & (p < hi)
+            block[row, p[keep] - lo] += S[k][keep]
+        else:
+            tail_part[off] += S[k][nodes >= a].sum()
+    for r, c, x in zip(inst_rows, inst_cols,
+                       np.asarray(inst_values, dtype=float)):
+        for at_, other in ((r, c),) if r == c else ((r, c), (c, r)):
+            if at_ >= tail:
+                if tail_owner:
+                    tail_part[at_ - tail] += x*v[other]
+            else:
+                R, p = divmod(int(at_), N)
+                if lo <= p < hi:
+                    block[R, p - lo] += x*v[other]
+    return block, tail_part
+
+
 #: nodes a block of ``opty_hesscsr`` advances by (64 lanes, one repeated node)
 HESSCSR_STRIDE = 63
 

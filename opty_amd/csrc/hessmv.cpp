@@ -23,6 +23,14 @@
 // a later block repeats the previous block's last node and counts as zero in
 // the tail sums.  Every element of y is stored once; no atomics.
 //
+// A window [wa, wb) of the constraint nodes (opty_hip_hessmv_apply_shard): the
+// same lanes from the GLOBAL v at the global node index.  Block B starts at
+// node wa - (wa > 0) + 63 B -- a window that does not start the problem begins
+// one (halo) node early, whose S_R1 the first owned time node needs --, stores
+// the time nodes p in [wa, pend), pend = wb + (wb == N - 1), at y[R*ostride +
+// p - wa], and its tail partials cover the nodes [wa, wb).  The window is
+// wave-uniform; the whole problem is the window [0, N - 1) with ostride = N.
+//
 // Block products Y = H V (opty_hip_hessmv_apply_block): opty_hessmv_block<K>
 // keeps K columns in flight -- K values of v and K accumulators per side and
 // lane -- so that a value goes through the tile once for all K; per column the
@@ -55,6 +63,9 @@ struct MvArgs {
     const int *sides;       // (row, slot) per side; row -1: (-1, tail offset)
     const int *rowside;     // side of (R, 0) and (R, 1) per trajectory row, or -1
     long long N;
+    // the window: constraint nodes [wa, wb), owned time nodes [wa, pend); val
+    // starts at node wa - (wa > 0), y at time node wa, rows ostride apart
+    long long wa, wb, pend, ostride;
     int PH, E, nS, nT, nrows;
 };
 
@@ -68,15 +79,18 @@ opty_hessmv(MvArgs a) {
     double *vs = lds + 64*kPitch;             // [nA][64]
     double *acc = vs + (size_t)nA*64;         // [nA][64]
     const long long N = a.N, ncn = N - 1;
-    const long long i0 = (long long)blockIdx.x*kStride;
+    const long long lo = a.wa - (a.wa > 0 ? 1 : 0);
+    const long long i0 = lo + (long long)blockIdx.x*kStride;
     const long long i = i0 + lane;
-    const bool valid = i < ncn;
+    const bool valid = i < a.wb;
     const long long tail = (long long)a.nrows*N;
-    // nodes of this block that exist (>= 1: i0 < ncn for every block)
-    const int nv = (int)(ncn - i0 < 64 ? ncn - i0 : 64);
+    // nodes of this block that exist (>= 1: i0 < wb for every block)
+    const int nv = (int)(a.wb - i0 < 64 ? a.wb - i0 : 64);
+    // lane 0 is the halo node, or repeats the previous block's last node
+    const bool first = lane > 0 || (blockIdx.x == 0 && a.wa == 0);
 
     // v at every side (a coalesced row load; tail sides broadcast), zero
-    // accumulators.  i < ncn: row*N + i + slot <= row*N + N - 1.
+    // accumulators.  i < wb <= ncn: row*N + i + slot <= row*N + N - 1.
     for (int s = 0; s < nA; ++s) {
         const int row = a.sides[2*s], off = a.sides[2*s + 1];
         double x = 0.0;
@@ -89,7 +103,7 @@ opty_hessmv(MvArgs a) {
     // node section: the block's nv*PH values are contiguous; a chunk is kChunk
     // entries of every node, loaded as rows of w consecutive doubles (two
     // nodes per wave instruction), read back lane = node
-    const double *blk = a.val + i0*a.PH;
+    const double *blk = a.val + (i0 - lo)*a.PH;
     const int half = lane >> 5, col = lane & 31;
     for (int c0 = 0; c0 < a.PH; c0 += kChunk) {
         const int w = a.PH - c0 < kChunk ? a.PH - c0 : kChunk;
@@ -116,19 +130,20 @@ opty_hessmv(MvArgs a) {
     __syncthreads();
 
     // trajectory rows: p = i; S_R0 of this lane + S_R1 of the lane before
-    const bool writes = (lane > 0 || blockIdx.x == 0) && i <= ncn;
+    const bool writes = first && i < a.pend;
     for (int R = 0; R < a.nrows; ++R) {
         const int s0 = a.rowside[2*R], s1 = a.rowside[2*R + 1];
         double x = 0.0;
         if (s0 >= 0) x = acc[s0*64 + lane];
         if (s1 >= 0 && lane > 0) x += acc[s1*64 + lane - 1];
-        if (writes) a.y[(long long)R*N + i] = x;
+        if (writes) a.y[(long long)R*a.ostride + (i - a.wa)] = x;
     }
 
-    // tail sides: a fixed tree over the lanes; the repeated node counts once
+    // tail sides: a fixed tree over the lanes; the halo node is another
+    // window's and the repeated node counts once
     for (int t = 0; t < a.nT; ++t) {
         double x = acc[(a.nS + t)*64 + lane];
-        if (lane == 0 && blockIdx.x > 0) x = 0.0;
+        if (!first) x = 0.0;
         for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d);
         if (lane == 0) a.part[(long long)blockIdx.x*a.nT + t] = x;
     }
@@ -140,16 +155,22 @@ struct FinArgs {
     const double *pval;
     const double *v;
     double *y;
+    double *tail_part;      // ntail doubles, by tail offset
     const int *sides;
     const long long *irows, *icols, *prows, *pcols;
     long long nblk, tail;
-    int nS, nT, ntail, nnz_inst, T;
+    // the window (MvArgs); owner: this call adds the explicit triplets' tail
+    // sides.  opty_hessmv_block_fin serves the whole problem only.
+    long long N, wa, pend, ostride;
+    int nS, nT, ntail, nnz_inst, T, owner;
 };
 
-// One wave, enqueued behind opty_hessmv: the tail entries of y (block
+// One wave, enqueued behind opty_hessmv: the tail entries (the window's block
 // partials added in block order; an entry without a side is 0.0), then one
 // lane applies the explicit triplets in stored order -- to the tail entries
-// in LDS, to trajectory entries (which opty_hessmv stored) in place.
+// in LDS when the call owns the tail, to the trajectory entries the window
+// owns (which opty_hessmv stored) in place; every other side is another
+// window's.
 __global__ void __launch_bounds__(64)
 opty_hessmv_fin(FinArgs a) {
     extern __shared__ double tl[];          // [ntail]
@@ -163,9 +184,18 @@ opty_hessmv_fin(FinArgs a) {
     }
     __syncthreads();
     if (lane == 0) {
+        // (the whole problem: y[R*N + p] without the division)
+        const bool whole = a.wa == 0 && a.pend == a.N && a.ostride == a.N;
         auto add = [&](long long at, double x) {
-            if (at >= a.tail) tl[at - a.tail] += x;
-            else a.y[at] += x;
+            if (at >= a.tail) {
+                if (a.owner) tl[at - a.tail] += x;
+            } else if (whole) {
+                a.y[at] += x;
+            } else {
+                const long long R = at/a.N, p = at - R*a.N;
+                if (p >= a.wa && p < a.pend)
+                    a.y[R*a.ostride + (p - a.wa)] += x;
+            }
         };
         auto apply = [&](long long r, long long c, double x) {
             add(r, x*a.v[c]);
@@ -177,7 +207,7 @@ opty_hessmv_fin(FinArgs a) {
             apply(a.prows[k], a.pcols[k], a.pval[k]);
     }
     __syncthreads();
-    for (int j = lane; j < a.ntail; j += 64) a.y[a.tail + j] = tl[j];
+    for (int j = lane; j < a.ntail; j += 64) a.tail_part[j] = tl[j];
 }
 
 // ---- K columns per pass ------------------------------------------------------
@@ -360,6 +390,14 @@ struct opty_hip_hessmv : Borrowed {
     size_t cap_v = 0, cap_y = 0;
     long long ncn() const { return p->d.N - 1; }
     long long blocks() const { return (ncn() + kStride - 1)/kStride; }
+    // time nodes the non-empty window [wa, wb) owns end here
+    long long pend(long long wb) const { return wb + (wb == ncn() ? 1 : 0); }
+    // blocks of a non-empty window: block 0 of a window that starts the
+    // problem stores 64 time nodes, every other block 63 (at most blocks())
+    long long blocks(long long wa, long long wb) const {
+        const long long todo = pend(wb) - wa - (wa == 0 ? 1 : 0);
+        return std::max(1LL, (todo + kStride - 1)/kStride);
+    }
     int nrows() const { return p->d.n + p->d.q; }
     int ntail() const { return p->d.r + p->d.s; }
     int64_t nnz() const {
@@ -408,6 +446,11 @@ MvArgs main_args(const opty_hip_hessmv *h, const double *values,
     a.sides = h->d_sides;
     a.rowside = h->d_rowside;
     a.N = h->p->d.N;
+    // the whole problem
+    a.wa = 0;
+    a.wb = h->ncn();
+    a.pend = a.N;
+    a.ostride = a.N;
     a.PH = h->d.PH;
     a.E = h->d.E;
     a.nS = h->nS;
@@ -436,6 +479,11 @@ FinArgs fin_args(const opty_hip_hessmv *h, const double *values,
     f.pcols = h->d_pcols;
     f.nblk = h->blocks();
     f.tail = (long long)h->nrows()*h->p->d.N;
+    // the whole problem: the tail entries end y, and the call owns them
+    f.tail_part = out + f.tail;
+    f.N = f.pend = f.ostride = h->p->d.N;
+    f.wa = 0;
+    f.owner = 1;
     f.nS = h->nS;
     f.nT = h->nT;
     f.ntail = h->ntail();
@@ -654,6 +702,90 @@ int opty_hip_hessmv_apply(opty_hip_hessmv *h, const double *values,
         if (int rc = stage_out(h, y, h->d_y, nfree*sizeof(double))) return rc;
         return host_done(h);
     }
+    return 0;
+}
+
+int opty_hip_hessmv_apply_shard(opty_hip_hessmv *h,
+                                const double *values_shard,
+                                const double *inst_values, const double *v,
+                                double *out, int64_t out_stride,
+                                double *tail_part, int64_t node_begin,
+                                int64_t node_end, int32_t tail_owner) {
+    if (!h || !values_shard || !v || !out) return fail("null argument");
+    if (h->d.E != 0 || h->d.T != 0)
+        return fail("the handle has an objective section (E %d, T %d): only "
+                    "the constraint section is node-sharded", h->d.E, h->d.T);
+    if (h->d.nnz_inst > 0 && !inst_values)
+        return fail("null inst_values, but the handle has %d instance "
+                    "entries", h->d.nnz_inst);
+    if (h->ntail() > 0 && !tail_part)
+        return fail("null tail_part, but the problem has %d tail entries",
+                    h->ntail());
+    const int64_t wa = node_begin, wb = node_end;
+    if (wa < 0 || wb > (int64_t)h->ncn() || wa > wb)
+        return fail("node window [%lld, %lld) is not within the %lld "
+                    "constraint nodes", (long long)wa, (long long)wb,
+                    h->ncn());
+    // the time nodes the window owns: the last window also owns node N - 1
+    const int64_t pend = wb > wa ? (int64_t)h->pend(wb) : wb;
+    const int64_t owned = pend - wa;
+    if (out_stride < owned)
+        return fail("out_stride %lld < the %lld time nodes the window owns",
+                    (long long)out_stride, (long long)owned);
+    const int nrows = h->nrows();
+    if (wb > wa && nrows > 0) {
+        auto meets = [](const double *a, size_t na, const double *b,
+                        size_t nb) {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return a0 < b0 + nb*sizeof(double) && b0 < a0 + na*sizeof(double);
+        };
+        const size_t no = (size_t)(nrows - 1)*(size_t)out_stride +
+                          (size_t)owned,
+                     nval = (size_t)(wb - wa + (wa > 0 ? 1 : 0))*
+                            (size_t)h->d.PH;
+        if (meets(out, no, v, (size_t)h->p->num_free()))
+            return fail("out (%d rows, out_stride %lld) overlaps v", nrows,
+                        (long long)out_stride);
+        if (nval && meets(out, no, values_shard, nval))
+            return fail("out (%d rows, out_stride %lld) overlaps the %zu "
+                        "values of the shard", nrows, (long long)out_stride,
+                        nval);
+    }
+    if (int rc = borrowed_begin(h, OPTY_HIP_DEVICE, false)) return rc;
+    const bool fin = h->ntail() > 0 || h->d.nnz_inst > 0;
+    FinArgs f = fin_args(h, values_shard, v, out);
+    f.ival = inst_values;
+    f.pval = nullptr;
+    f.tail_part = tail_part;
+    f.wa = wa;
+    f.pend = pend;
+    f.ostride = out_stride;
+    f.owner = tail_owner != 0;
+    if (wa == wb) {
+        // nothing to evaluate: the window's share of the tail sums is zero
+        // (all bits clear), on top of which the owner's explicit triplets go
+        if (h->ntail() > 0)
+            HIP_TRY(hipMemsetAsync(tail_part, 0,
+                                   (size_t)h->ntail()*sizeof(double),
+                                   h->stream));
+        if (!(f.owner && h->d.nnz_inst > 0)) return 0;
+        f.nblk = 0;
+    } else {
+        MvArgs a = main_args(h, values_shard, v, out);
+        a.oval = nullptr;
+        a.wa = wa;
+        a.wb = wb;
+        a.pend = pend;
+        a.ostride = out_stride;
+        f.nblk = h->blocks(wa, wb);
+        hipLaunchKernelGGL(opty_hessmv, dim3((unsigned)f.nblk), dim3(64),
+                           h->lds_main, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        if (!fin) return 0;
+    }
+    hipLaunchKernelGGL(opty_hessmv_fin, dim3(1), dim3(64), h->lds_fin,
+                       h->stream, f);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -3956,11 +3956,15 @@ class ShardedProblem(Problem):
     known trajectories given as functions of ``free``) is refused by the
     constructor on every rank, before any collective; so is ``obj_hessian``
     in a process without an initialised ``torch.distributed`` group
-    (``NotImplementedError``: there are no ranks to serve it).  Not sharded:
-    ``H v``
-    from shards that stay in device memory (:meth:`hessian_operator`
-    refuses), the objective's Hessian, block products; the torch-free host
-    (``shard_host.py``) and the C client do not serve the Hessian.
+    (``NotImplementedError``: there are no ranks to serve it).
+
+    :meth:`resident_hessian_operator` gives ``H v`` from shards that stay in
+    device memory: one load, then one round of
+    ``num_free`` doubles each way per product; :meth:`hessian_operator`
+    itself keeps refusing.  Not sharded: the objective's Hessian (the root
+    alone evaluates and multiplies it), block products, ``hessian_csr`` /
+    ``kkt_csr``; the torch-free host (``shard_host.py``) and the C client
+    do not serve the Hessian.
 
     Extra keywords: ``group`` (process group), ``root`` (solver rank),
     ``torch_device`` (default ``cuda:<device>``), ``sharded_kwargs`` (further
@@ -4020,6 +4024,8 @@ class ShardedProblem(Problem):
             self._objective_hessian_of(obj_hessian)
         cb, col = self.callbacks, self.collocator
         cb.hessian_extra = len(rows)
+        # (what resident_hessian_operator needs of the objective)
+        self._objective_parts = (rows, values, device_backed)
         if not cb.is_root:
             return
         num_con = self.sharded.hessian_nnz
@@ -4094,6 +4100,136 @@ class ShardedProblem(Problem):
             rows, cols = self.collocator.jacobian_indices()
         return (self.callbacks.constraints, self.callbacks.jacobian, rows,
                 cols)
+
+    def _resident_objective(self):
+        """Root: ``(values, product handle)`` of the objective section of
+        :meth:`resident_hessian_operator`, or None for an ``obj_hessian``
+        without entries.  Refuses, before any collective, what
+        ``Problem.hessian_operator`` refuses."""
+        parts = getattr(self, '_objective_parts', None)
+        if parts is None:
+            raise NotImplementedError(
+                'ShardedProblem.resident_hessian_operator needs a problem '
+                'built with obj_hessian=(rows, cols, values): the ranks '
+                'agree on the Hessian at construction, before any '
+                'collective.')
+        rows, values, device_backed = parts
+        if not len(rows):
+            return None
+        if not device_backed:
+            raise TypeError(
+                'ShardedProblem.resident_hessian_operator needs an '
+                'obj_hessian whose values have a device handle '
+                '(values.handle: opty_amd.create_objective_hessian_'
+                'function); a hand-written values callable has no index '
+                'pattern to multiply with.')
+        col = self.collocator
+        objective = values.handle
+        prog = col._build_hessian_program()
+        want = dict(N=col.num_collocation_nodes, n=prog.n, q=prog.q,
+                    r=prog.r)
+        have = {k: objective.desc[k] for k in want}
+        if have != want or prog.s:
+            raise ValueError(
+                'the objective Hessian was built for %s, the problem has %s'
+                % (have, dict(want, s=prog.s)))
+        if getattr(self, '_resident_objective_of', None) is not objective:
+            # the objective section alone (PH = 0), over the root's problem
+            # handle
+            tail = (prog.n + prog.q)*col.num_collocation_nodes
+            self._resident_objective_handle = hb.HipHessianProduct(
+                col.hip, dict(obj_pattern=objective.pattern,
+                              obj_base=objective.desc['base'],
+                              tail_rows=tail + objective.tail_pairs[:, 0],
+                              tail_cols=tail + objective.tail_pairs[:, 1]))
+            self._resident_objective_of = objective
+        return values, self._resident_objective_handle
+
+    def resident_hessian_operator(self, free, lagrange, obj_factor=1.0):
+        """Root: the Hessian of the Lagrangian at ``(free, lagrange,
+        obj_factor)`` as a symmetric ``scipy.sparse.linalg.LinearOperator``
+        of shape ``(num_free, num_free)`` whose values never leave the GPUs
+        (the serving ranks answer from
+        :meth:`serve`).  The call loads the values ONCE: every rank
+        evaluates the constraint triplets of its own nodes, and of one halo
+        node, into its device memory
+        (:meth:`opty_amd.sharded.ShardedCallbacks.hessian_load`); every
+        ``matvec`` is then one round in which each rank multiplies its
+        window (``opty_hip_hessmv_apply_shard``) and ``num_free`` doubles
+        travel each way.  The trajectory entries of the constraint part have
+        the bits of the single-GPU ``hessian_operator``'s, its
+        node-invariant tail is the sum of the ranks' shares in rank order.
+        ``matmat`` loops over the columns: block products are not sharded.
+
+        The objective section is the root's alone: it evaluates the
+        objective's values into a device buffer of its own and multiplies
+        them with an objective-only product handle; the result is
+        ``y_con + y_obj``, one rounding per element.  This needs a
+        device-backed ``obj_hessian``
+        (``opty_amd.create_objective_hessian_function``) -- anything else is
+        refused as ``Problem.hessian_operator`` refuses it, before any
+        collective --; an ``obj_hessian`` without entries skips the section.
+
+        Host arrays only (``TypeError`` for a CUDA tensor).  The name
+        differs from :meth:`hessian_operator` because the contract does: the
+        values live on all ranks and ONE set is resident at a time.  A later
+        ``resident_hessian_operator`` (or ``callbacks.hessian_load``)
+        replaces it; a product through an older operator then raises
+        ``RuntimeError``."""
+        from scipy.sparse.linalg import LinearOperator
+        if on_device(free) or on_device(lagrange):
+            raise TypeError(
+                'ShardedProblem.resident_hessian_operator takes host arrays '
+                'only: the vectors travel through host memory shared by the '
+                'ranks; pass NumPy arrays (free.cpu().numpy()).')
+        objective = self._resident_objective()
+        cb, col, sh = self.callbacks, self.collocator, self.sharded
+        free = col._host_free(free)
+        nfree = sh._num_free()
+        generation = cb.hessian_load(free, lagrange)
+        obj_values = None
+        if objective is not None:
+            import torch
+            values, handle = objective
+            obj_values = torch.empty(handle.nnz, dtype=torch.float64,
+                                     device=sh.device)
+            # (cb.free_dev: where the load left free on the root's GPU)
+            values(cb.free_dev, obj_factor, obj_values)
+            y_obj = torch.empty(nfree, dtype=torch.float64, device=sh.device)
+
+        def product(x):
+            y = cb.hmv(np.asarray(x, dtype=np.float64).reshape(-1),
+                       generation)
+            if obj_values is None:
+                return y
+            # (cb._hv_dev: where the round left v on the root's GPU)
+            import torch
+            sh._use_stream()
+            handle.apply(obj_values, cb._hv_dev, y_obj, hb.DEVICE)
+            torch.cuda.synchronize(sh.device)
+            return y + y_obj.cpu().numpy()
+
+        class ResidentHessianOperator(LinearOperator):
+            def __init__(op):
+                super().__init__(np.dtype(np.float64), (nfree, nfree))
+
+            def _matvec(op, x):
+                return product(x)
+
+            _rmatvec = _matvec
+
+            def _matmat(op, X):
+                X = np.asarray(X, dtype=np.float64)
+                out = np.empty((nfree, X.shape[1]))
+                for c in range(X.shape[1]):
+                    out[:, c] = product(X[:, c])
+                return out
+
+            _rmatmat = _matmat
+
+        op = ResidentHessianOperator()
+        op.generation = generation
+        return op
 
     def jacobian_operator(self, free):
         """Root: the constraint Jacobian at ``free`` as the

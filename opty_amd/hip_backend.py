@@ -601,6 +601,9 @@ _SIGNATURES = {
                                      ctypes.c_int64, ctypes.c_int32,
                                      ctypes.c_int32]),
     'opty_hip_hessmv_block_width': (ctypes.c_int32, [_P]),
+    'opty_hip_hessmv_apply_shard': (ctypes.c_int, [
+        _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64,
+        ctypes.c_int64, ctypes.c_int32]),
     'opty_hip_hesscsr_create': (ctypes.c_int,
                                 [_P, ctypes.POINTER(_HessmvDesc),
                                  ctypes.POINTER(_P)]),
@@ -1608,6 +1611,18 @@ class HipHessianProduct(_HessianTripletsHandle):
         _check(self._lib.opty_hip_hessmv_apply_block(
             self._handle(), _ptr(values), _ptr(V), int(ldv), _ptr(Y),
             int(ldy), int(ncols), mem))
+
+    def apply_shard(self, values_shard, inst_values, v, out, out_stride,
+                    tail_part, node_begin, node_end, tail_owner):
+        """The share of ``H v`` of the constraint nodes ``[node_begin,
+        node_end)`` from the global device ``v`` and the window's values (one
+        halo node in front when ``node_begin > 0``): the owned time nodes
+        into ``out``, the share of the tail entries into ``tail_part``; see
+        ``opty_hip_hessmv_apply_shard`` in ``include/opty_hip.h``."""
+        _check(self._lib.opty_hip_hessmv_apply_shard(
+            self._handle(), _ptr(values_shard), _ptr(inst_values), _ptr(v),
+            _ptr(out), int(out_stride), _ptr(tail_part), int(node_begin),
+            int(node_end), int(bool(tail_owner))))
 
 
 class HipHessianCsr(_HessianTripletsHandle):

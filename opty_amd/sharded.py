@@ -61,6 +61,15 @@ ADD -- rank ``g`` writes the contiguous slice ``[a_g*PH, b_g*PH)``, there is
 no halo node and no sum across ranks, and every value has the bits of the
 whole-problem evaluation.  The instance entries follow the node blocks and
 are evaluated by :attr:`ShardedCollocator.tail_rank`.
+
+The Hessian OPERATOR of a sharded problem multiplies values that never leave
+the devices (:meth:`ShardedCollocator.hessian_load` /
+:meth:`ShardedCollocator.hmv`, ``opty_hip_hessmv_apply_shard``, DESIGN.md
+section 11.3): a load leaves the values of rank ``g``'s nodes and of one halo
+node, ``[a_g - (a_g > 0), b_g)``, resident in its memory; a product computes
+the entries of ``H v`` at the time nodes the rank owns -- bit for bit those
+of the whole-problem product -- and its share of the node-invariant tail,
+which is added in rank order as for ``J^T w``.
 """
 
 import os
@@ -317,6 +326,12 @@ class ShardedCollocator(object):
     ``(b - a)*PH`` values of the window's nodes and, where ``inst_out`` is
     not None, the ``nnz_inst`` instance values.
 
+    ``hessian_product_evaluator``: ``f(values, inst, v, out2d, tail_part, a,
+    b, tail_owner)`` in place of the HIP Hessian-product kernels
+    (:meth:`hmv`; CPU tests): from the resident values of the nodes ``[a -
+    (a > 0), b)``, the instance values and the global ``v`` it fills the
+    ``(n + q, owned)`` block and the ``r + s`` tail shares.
+
     The known maps are re-read on every :meth:`evaluate` (the reference reads
     them on every call, ``opty/direct_collocation.py:2891-2926``), callable
     known trajectories are evaluated on the host from ``free``.
@@ -330,7 +345,8 @@ class ShardedCollocator(object):
                  instance_constraints=None, rank=None, world_size=None,
                  group=None, device=None, evaluator=None, block_shape=None,
                  instance_evaluator=None, comm=None, product_evaluator=None,
-                 hessian_evaluator=None, **kwargs):
+                 hessian_evaluator=None, hessian_product_evaluator=None,
+                 **kwargs):
         import torch
         #: ``hip_backend.HipComm`` (or None): when given -- and the HIP
         #: evaluator is in use -- :meth:`broadcast_free` and :meth:`gather` go
@@ -410,6 +426,14 @@ class ShardedCollocator(object):
         #: buffers and handle of the Hessian (made by the first Hessian call)
         self.hess_local = self.hess_inst = None
         self._hessian_handle = None
+        if self._hip_mode:
+            hessian_product_evaluator = self._hip_hmv
+        self._hessian_product = hessian_product_evaluator
+        #: resident values, results and handle of the Hessian operator (made
+        #: by the first :meth:`hessian_load`); the generation counts the loads
+        self.hmv_values = self.hmv_inst = self.hmv_local = self.hmv_tail = None
+        self._hmv_handle = None
+        self.hessian_generation = 0
         cnt = self.b - self.a
         f64 = dict(dtype=torch.float64, device=self.device)
         self.con_local = torch.empty((self.M, cnt), **f64)
@@ -646,18 +670,22 @@ class ShardedCollocator(object):
         1``.  The ranges of all ranks tile ``[0, N)``."""
         return self.a, self.b + (1 if self.b == self.N - 1 else 0)
 
+    def _free_layout(self):
+        """``num_tail``: the ``r + s`` node-invariant entries that end the
+        free vector; ``num_rows``: the ``n + q`` trajectory rows of ``N``
+        entries that precede them."""
+        col = self.collocator
+        self.num_tail = len(col.unknown_parameters) + \
+            int(bool(col._variable_duration))
+        self.num_rows = (col.num_free - self.num_tail)//self.N
+
     def _product_buffers(self):
         """The rank-local results of the products, allocated on first use (a
         collocator that is never asked for products holds none)."""
         if self.jv_local is None:
             import torch
-            col = self.collocator
             f64 = dict(dtype=torch.float64, device=self.device)
-            #: ``r + s`` node-invariant entries end the free vector; ``n + q``
-            #: trajectory rows of ``N`` entries precede them
-            self.num_tail = len(col.unknown_parameters) + \
-                int(bool(col._variable_duration))
-            self.num_rows = (col.num_free - self.num_tail)//self.N
+            self._free_layout()
             lo, hi = self.owned_nodes
             self.jv_local = torch.empty((self.M, self.b - self.a), **f64)
             self.jv_inst = torch.empty(self.o, **f64)
@@ -881,6 +909,111 @@ class ShardedCollocator(object):
         cols = np.empty(count, dtype=np.int64)
         handle.indices_range(self.a, self.b, rows, cols, hb.HOST)
         return rows, cols
+
+    # -- Hessian operator: H v from resident values (no collective) -----------------
+    @property
+    def halo_begin(self):
+        """First constraint node of the resident values: entry ``p`` of a
+        trajectory row of ``H v`` needs node ``p - 1`` too, so a rank that
+        does not start the problem holds one (halo) node in front."""
+        return self.a - (1 if self.a > 0 else 0)
+
+    def _hmv_buffers(self):
+        """The resident values and the rank-local results of the Hessian
+        operator, allocated by the first load (a collocator that is never
+        asked for it holds none)."""
+        if self.hmv_values is None:
+            import torch
+            self._hessian_sizes()
+            self._free_layout()
+            f64 = dict(dtype=torch.float64, device=self.device)
+            lo, hi = self.owned_nodes
+            self.hmv_values = torch.empty(
+                (self.b - self.halo_begin)*self.PH, **f64)
+            self.hmv_inst = torch.empty(self.hess_nnz_inst, **f64)
+            self.hmv_local = torch.empty((self.num_rows, hi - lo), **f64)
+            self.hmv_tail = torch.empty(self.num_tail, **f64)
+
+    def _hip_hmv(self, values, inst, v, out2d, tail_part, a, b, tail_owner):
+        if self._hmv_handle is None:
+            self._use_stream()
+            self._hmv_handle = self.collocator._ensure_hessmv()
+        self._use_stream()
+        self._hmv_handle.apply_shard(
+            values, inst if inst.numel() else None, v, out2d,
+            out2d.stride(0), tail_part if tail_part.numel() else None, a, b,
+            tail_owner)
+
+    def hessian_load(self, free, lagrange, sync=True):
+        """Evaluates the values of the Hessian of the constraint Lagrangian
+        at the global ``(free, lagrange)`` that this rank's products need --
+        its constraint nodes and one halo node in front, ``[halo_begin,
+        b)``, every value bit for bit the whole-problem evaluation's; the
+        instance values on EVERY rank (one lane, from the global vectors) --
+        into resident buffers of this object, which :meth:`hmv` reads until
+        the next load replaces them.  Nothing leaves the device.  Returns
+        :attr:`hessian_generation`, which every load bumps.  ``sync`` as in
+        :meth:`evaluate`."""
+        if self._hessian is None or self._hessian_product is None:
+            raise ValueError('a collocator with an injected evaluator needs '
+                             'hessian_evaluator and hessian_product_evaluator '
+                             'for the Hessian operator')
+        if free.numel() != self._num_free():
+            raise ValueError('free must have {} entries, got {}'.format(
+                self._num_free(), free.numel()))
+        if lagrange.numel() != self.num_constraints:
+            raise ValueError('lagrange must have {} entries, got {}'.format(
+                self.num_constraints, lagrange.numel()))
+        self._hmv_buffers()
+        if self._hip_mode:
+            self._hip_hessian_handle()
+        if sync:
+            self.sync_known(free)
+        self._hessian(free, lagrange, self.hmv_values,
+                      self.hmv_inst if self.hess_nnz_inst else None,
+                      self.halo_begin, self.b)
+        self.hessian_generation += 1
+        return self.hessian_generation
+
+    def hmv(self, v, sync=True):
+        """This rank's share of ``H v`` from the resident values of the last
+        :meth:`hessian_load` and the global ``v`` (``num_free`` doubles, on
+        this rank's device): ``(block, tail_part)`` -- ``block`` is ``(n + q,
+        owned)``, row ``R`` = the entries ``[R*N + lo, R*N + hi)`` of the
+        single-GPU product, bit for bit (:attr:`owned_nodes`; the instance
+        triplets' terms at owned entries included); ``tail_part`` this rank's
+        share of the ``r + s`` node-invariant entries, on :attr:`tail_rank`
+        with the instance triplets' tail terms.  The entries themselves are
+        the sum of the ranks' shares IN RANK ORDER (:meth:`sum_tail_parts`).
+        Buffers of this object, which the next call overwrites.  A product
+        reads no known map: ``sync`` is accepted for the signature of
+        :meth:`jvp` / :meth:`vjp` and changes nothing."""
+        if self.hmv_values is None:
+            raise RuntimeError('no resident Hessian values: call '
+                               'hessian_load(free, lagrange) first')
+        if v.numel() != self._num_free():
+            raise ValueError('v must have {} entries, got {}'.format(
+                self._num_free(), v.numel()))
+        self._hessian_product(self.hmv_values, self.hmv_inst, v,
+                              self.hmv_local, self.hmv_tail, self.a, self.b,
+                              self.rank == self.tail_rank)
+        return self.hmv_local, self.hmv_tail
+
+    def hmv_to_host(self, y_host, tails_host):
+        """Copies the last :meth:`hmv` into the node-wide host vector
+        ``y_host`` (``num_free`` doubles: row ``R`` to ``[R*N + lo, R*N +
+        hi)``) and its tail shares into row ``rank`` of ``tails_host``
+        (``world_size*(r + s)`` doubles); both :class:`SharedHostVector`, as
+        in :meth:`products_to_host`.  Enqueued on the current stream:
+        synchronise it before reading.  The tail of ``y_host`` is for the
+        assembling rank to fill (:meth:`sum_tail_parts`)."""
+        lo, hi = self.owned_nodes
+        R, T = self.num_rows, self.num_tail
+        y_host.torch_view(0, R*self.N).view(R, self.N)[:, lo:hi].copy_(
+            self.hmv_local, non_blocking=True)
+        if T:
+            tails_host.torch_view(self.rank*T, (self.rank + 1)*T).copy_(
+                self.hmv_tail, non_blocking=True)
 
     def broadcast_free(self, free, src=0):
         """RCCL broadcast of the global free vector from rank ``src`` (18 MB
@@ -1155,9 +1288,16 @@ class ShardedCallbacks(object):
     returns.  ``hessian_extra``: doubles to keep free behind the constraint
     section of that vector (``ShardedProblem`` puts the objective's values
     there).  The vectors of this command are created by its first round.
+
+    :meth:`hessian_load` / :meth:`hmv` serve the Hessian OPERATOR from values
+    that stay on the devices: a load leaves every
+    rank's values of the constraint Lagrangian's Hessian resident in its own
+    memory, a product moves ``num_free`` doubles each way.  Their vectors are
+    created by the first load.
     """
 
     _STOP, _CON, _JAC, _BOTH, _JVP, _VJP, _HESS = 0, 1, 2, 3, 4, 5, 6
+    _HLOAD, _HMV = 7, 8
 
     def __init__(self, sharded, name=None, root=0, pin=True,
                  fresh_constraints=True, jac_host=None, hessian_extra=0):
@@ -1222,6 +1362,9 @@ class ShardedCallbacks(object):
         # the Hessian's vectors: made by the first Hessian command
         self.hessian_extra = int(hessian_extra)
         self._lam_dev = self.lam_host = self.hess_host = None
+        # the Hessian operator's vectors: made by its first load
+        self._hv_dev = self._hlam_dev = None
+        self.hv_host = self.hlam_host = self.hy_host = self.htails_host = None
 
     # -- one evaluation, on every rank ------------------------------------------
     def _known_updates(self, free):
@@ -1374,12 +1517,81 @@ class ShardedCallbacks(object):
             torch.cuda.synchronize(sh.device)
         self._dist.barrier(sh.group)            # every slice has landed
 
+    def _operator_vectors(self):
+        """The vectors of the Hessian operator, on every rank in the same
+        round (their creation is collective): the multipliers and the
+        direction on the device and, under gloo, in shared host memory; the
+        result and the ranks' tail shares in shared host memory.  No vector
+        of the size of the values: those stay on the devices."""
+        if self.hy_host is not None:
+            return
+        import torch
+        sh = self.sh
+        sh._hmv_buffers()
+        nfree, ncon = self.num_free, sh.num_constraints
+        f64 = dict(dtype=torch.float64, device=sh.device)
+        self._hlam_dev = torch.empty(ncon, **f64)
+        self._hv_dev = torch.empty(nfree, **f64)
+        kw = dict(pin=self._pin, **self._shm)
+        if not self._rccl:
+            self.hlam_host = SharedHostVector(self._name + '_hlam', ncon,
+                                              sh.rank, **kw)
+            self.hv_host = SharedHostVector(self._name + '_hv', nfree,
+                                            sh.rank, **kw)
+        self.hy_host = SharedHostVector(self._name + '_hy', nfree, sh.rank,
+                                        **kw)
+        self.htails_host = SharedHostVector(
+            self._name + '_htails', max(1, sh.world_size*sh.num_tail),
+            sh.rank, **kw)
+
+    def _share_vector(self, dev, host):
+        """The root's pending vector reaches ``dev`` on every rank: broadcast
+        GPU to GPU under RCCL, through the shared vector ``host`` under gloo
+        (the root fills it here, and nobody reads it before the root
+        has)."""
+        import torch
+        if self._rccl:
+            if self.is_root:
+                dev.copy_(torch.from_numpy(self._pending_vec))
+            self._dist.broadcast(dev, self.root, group=self.sh.group)
+        else:
+            if self.is_root:
+                host.array[:] = self._pending_vec
+            self._dist.barrier(self.sh.group)
+            dev.copy_(host.torch_view(), non_blocking=True)
+
+    def _load_round(self, flags, params=None, traj=None):
+        import torch
+        sh = self.sh
+        self._operator_vectors()
+        self._share_known(flags, params, traj)
+        self._load_free()
+        self._share_vector(self._hlam_dev, self.hlam_host)
+        sh.hessian_load(self.free_dev, self._hlam_dev, sync=False)
+        if sh.device.type == 'cuda':
+            torch.cuda.synchronize(sh.device)
+        self._dist.barrier(sh.group)            # every rank holds its values
+
+    def _hmv_round(self):
+        import torch
+        sh = self.sh
+        self._share_vector(self._hv_dev, self.hv_host)
+        sh.hmv(self._hv_dev, sync=False)
+        sh.hmv_to_host(self.hy_host, self.htails_host)
+        if sh.device.type == 'cuda':
+            torch.cuda.synchronize(sh.device)
+        self._dist.barrier(sh.group)            # every slice has landed
+
     def _round(self, cmd, flags, params=None, traj=None):
         import torch
         if cmd in (self._JVP, self._VJP):
             return self._product_round(cmd, flags, params, traj)
         if cmd == self._HESS:
             return self._hessian_round(flags, params, traj)
+        if cmd == self._HLOAD:
+            return self._load_round(flags, params, traj)
+        if cmd == self._HMV:
+            return self._hmv_round()
         what = {self._CON: 'con', self._JAC: 'jac', self._BOTH: 'both'}[cmd]
         self._share_known(flags, params, traj)
         self._load_free()
@@ -1482,6 +1694,53 @@ class ShardedCallbacks(object):
         self._call(free, self._HESS, lagrange, 'lagrange')
         return self.hess_host.array
 
+    def hessian_load(self, free, lagrange):
+        """Makes the Hessian of the constraint Lagrangian at ``(free,
+        lagrange)`` resident on the ranks: ``free``
+        and ``lagrange`` take the routes they take for :meth:`hessian`, every
+        rank evaluates the values of its nodes and of one halo node into its
+        own device memory (:meth:`ShardedCollocator.hessian_load`), and
+        nothing comes back.  ONE set is resident: a later load replaces it.
+        Returns the generation of this set, for :meth:`hmv` to hold a caller
+        to."""
+        self._call(free, self._HLOAD, lagrange, 'lagrange')
+        return self.sh.hessian_generation
+
+    def hmv(self, v, generation=None):
+        """``H v`` from the resident values (``num_free`` doubles, ordered
+        like ``free``; a fresh array): ``v`` takes the route ``free`` takes,
+        every rank multiplies its window (:meth:`ShardedCollocator.hmv`) and
+        copies its slice into a shared host vector; the trajectory entries
+        are bit for bit those of the single-GPU product, the node-invariant
+        tail is the sum of the ranks' shares in rank order.  ``generation``:
+        what :meth:`hessian_load` returned for the values the caller means;
+        ``RuntimeError`` when another load has replaced them since."""
+        assert self.is_root, 'callbacks run on the root rank; others serve()'
+        sh = self.sh
+        if self.hy_host is None:
+            raise RuntimeError('no resident Hessian values: call '
+                               'hessian_load(free, lagrange) first')
+        if generation is not None and generation != sh.hessian_generation:
+            raise RuntimeError(
+                'the resident Hessian values were replaced: this product '
+                'belongs to load {}, the ranks hold load {} (one set is '
+                'resident at a time; make a new operator)'.format(
+                    generation, sh.hessian_generation))
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (self.num_free,):
+            raise ValueError('v must have shape ({},), got {}'.format(
+                self.num_free, v.shape))
+        self._pending_vec = v
+        self._command(self._HMV)
+        self._round(self._HMV, (0, 0))
+        self._pending_vec = None
+        out = np.array(self.hy_host.array)
+        if sh.num_tail:
+            parts = self.htails_host.array[:sh.world_size*sh.num_tail]
+            out[sh.num_rows*sh.N:] = sh.sum_tail_parts(
+                parts.reshape(sh.world_size, sh.num_tail))
+        return out
+
     def shutdown(self):
         """Releases the serving ranks (root only; idempotent)."""
         if self.is_root and self._cmd is not None:
@@ -1504,6 +1763,8 @@ class ShardedCallbacks(object):
         for v in (self.free_host, self.con_host,
                   self.jac_host if self._own_jac_host else None,
                   self.vec_host, self.jv_host, self.jtw_host,
-                  self.tails_host, self.lam_host, self.hess_host):
+                  self.tails_host, self.lam_host, self.hess_host,
+                  self.hv_host, self.hlam_host, self.hy_host,
+                  self.htails_host):
             if v is not None:
                 v.close()
