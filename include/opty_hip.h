@@ -183,7 +183,8 @@ typedef struct opty_hip_desc {
  * opty_hip_eval_hess_instance / opty_hip_hessian_indices_range, and then the
  * opty_hip_hesscsr_* entry points, and then
  * opty_hip_hesscsr_create_with_diagonal and the opty_hip_kktcsr_* entry
- * points, and then opty_hip_hessmv_apply_shard), and
+ * points, and then opty_hip_hessmv_apply_shard, and then the
+ * opty_hip_normal_* entry points), and
  * opty_hip_eval_jac_persistent / opty_hip_shard_jac_to_host took their `fresh`
  * argument in 4. */
 #define OPTY_HIP_ABI_VERSION 12
@@ -1216,6 +1217,96 @@ int opty_hip_kktcsr_assemble_timed(opty_hip_kktcsr *h,
                                    const double *sigma, double delta_w,
                                    double delta_c, double *data,
                                    float *stage_ms);
+
+/* ---- Normal matrix: a direct solve with the block-tridiagonal J D^-1 J^T ----
+ *
+ *     S = Jc[:, :T] diag(1/d[:T]) Jc[:, :T]^T + delta_c I
+ *
+ * Jc: the M(N-1) collocation rows of the constraint Jacobian, T = (n+q)N the
+ * trajectory part of `free`.  Constraint node i touches only the time nodes i
+ * and i + 1, so, ordered by node, S is symmetric block tridiagonal: N - 1
+ * diagonal blocks A_i (M x M, row-major) and N - 2 couplings B_i = S[i+1, i].
+ * With G_i the block of constraint node i (a structurally pruned entry is 0):
+ *
+ *   A_i[a,b] = sum_k G_i[a,k] G_i[b,k] / d[row_k*N + i + off_k]
+ *              (+ delta_c when a == b), over the trajectory columns k in
+ *              ascending (row, off);
+ *   B_i[a,b] = sum_row G_{i+1}[a,k0(row)] G_i[b,k1(row)] / d[row*N + i + 1],
+ *              over the free rows that have an offset-0 column k0 and an
+ *              offset-1 column k1 (backward Euler: the unknown inputs have no
+ *              offset-0 column and drop out).
+ *
+ * The tail columns (unknown parameters, a free interval) and the instance
+ * rows are NOT part of S: S is all of J D^-1 J^T only for a problem that has
+ * neither; otherwise it is a preconditioner (a low-rank correction for the
+ * tail is not done).  Every element is one chain of fma over the columns in
+ * the order above, the second factor divided by d first.
+ *
+ * Factorisation: block cyclic reduction with Cholesky factors of the
+ * eliminated diagonal blocks (normal_factor / normal_solve of
+ * opty_amd/codegen/program.py are the host statement): level l has n_l rows,
+ * n_0 = N - 1, n_{l+1} = ceil(n_l/2); rows 1, 3, 5, ... are eliminated, rows
+ * 0, 2, 4, ... survive as e = k/2; a level with one row is a plain Cholesky.
+ * No pivoting; backward stable for a positive definite S.  A pivot that is
+ * not positive and finite is replaced by 1 and recorded: the factorisation
+ * runs to its end, opty_hip_normal_factor_status names the smallest (level,
+ * row) that met one, and opty_hip_normal_solve refuses until a factorisation
+ * succeeds.  That is a numerical status, never a device fault.
+ *
+ * The handle owns all level storage (about 4 M^2 doubles per constraint node
+ * over all levels, plus three vectors per level):
+ * opty_hip_normal_workspace_bytes.  Creation refuses an M whose three M x (M|1)
+ * tiles of doubles exceed the LDS one block may use (82 with 160 KiB) and
+ * names the limit; opty_hip_normal_max_equations returns it.  The same inputs
+ * give the same bits in every call and for both memory kinds; nothing outside
+ * the handle's buffers and the outputs is written.  The handle BORROWS its
+ * problem handle (sizes, method, device, stream) and must be destroyed before
+ * it. */
+typedef struct opty_hip_normal_desc {
+    int32_t M;            /* rows of a block: equations of motion              */
+    int32_t P;            /* values stored per constraint node                 */
+    int32_t layout;       /* OPTY_HIP_LAYOUT_COO: jac[i*P + e]; OPTY_HIP_LAYOUT_CSR:
+                             jac[S_j*(N-1) + i*L_j + (e - S_j)], the entries
+                             grouped by equation, ascending                    */
+    const int32_t *pattern; /* (j, k) of every stored entry of a block in
+                             storage order, 2*P int32: equation, wrt column
+                             (of the problem handle's C)                       */
+} opty_hip_normal_desc;
+
+typedef struct opty_hip_normal opty_hip_normal;
+
+int opty_hip_normal_create(opty_hip_problem *p,
+                           const opty_hip_normal_desc *desc,
+                           opty_hip_normal **out);
+int opty_hip_normal_destroy(opty_hip_normal *h);
+/* device memory the handle owns for the levels and its tables */
+int64_t opty_hip_normal_workspace_bytes(const opty_hip_normal *h);
+/* the largest M creation accepts on the handle's device */
+int32_t opty_hip_normal_max_equations(const opty_hip_normal *h);
+/* jac_values: the P*(N-1) block values in the descriptor's layout (what
+ * follows them is not read); d: (n+q)*N doubles, positive (not checked), or
+ * NULL for all ones; A: (N-1)*M*M, B: (N-2)*M*M doubles (may be NULL when N ==
+ * 2); all in `mem` memory.  Synchronous for OPTY_HIP_HOST, enqueued on the
+ * problem's stream for OPTY_HIP_DEVICE.  Does not touch a factorisation.
+ * Refused before anything is enqueued: null pointers, a bad memory kind,
+ * delta_c < 0 or not finite, outputs that overlap an input or each other. */
+int opty_hip_normal_blocks(opty_hip_normal *h, const double *jac_values,
+                           const double *d, double delta_c, double *A,
+                           double *B, int32_t mem);
+/* Forms the blocks in the handle's storage and factorises them there. */
+int opty_hip_normal_factor(opty_hip_normal *h, const double *jac_values,
+                           const double *d, double delta_c, int32_t mem);
+/* Waits for the last factorisation: *level = -1 when every pivot was positive
+ * and finite, else the smallest (level, row of that level) that met one that
+ * was not.  Non-zero only without a factorisation. */
+int opty_hip_normal_factor_status(opty_hip_normal *h, int32_t *level,
+                                  int64_t *row);
+/* y = S^-1 r for ncols right-hand sides, column c at r + c*ld / y + c*ld, M(N-1)
+ * doubles each in the order of constraints(free), j*(N-1) + i; one column
+ * after the other.  Refused before anything is enqueued: null pointers, a bad
+ * memory kind, ld < M(N-1), y overlapping r, no successful factorisation. */
+int opty_hip_normal_solve(opty_hip_normal *h, const double *r, double *y,
+                          int32_t ncols, int64_t ld, int32_t mem);
 
 int opty_hip_device_count(void);
 const char *opty_hip_last_error(void);

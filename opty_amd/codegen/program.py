@@ -1209,6 +1209,210 @@ def assemble_kkt_csr(prog, N, hess_values, jac_values, pattern, inst_rows=(),
     return data
 
 
+def normal_columns(prog):
+    """What ``opty_hip_normal_create`` derives from a program's ``pattern``:
+    ``(sides, ent, coupled)`` -- ``sides``: the distinct trajectory sides
+    ``(row, off)`` of the stored entries in ascending order (the tail columns
+    are not part of the normal matrix); ``ent[j][c]``: the stored entry of
+    equation ``j`` in sorted column ``c`` or -1; ``coupled``: ``(c0, c1,
+    row)`` of every free row with an offset-0 column ``c0`` and an offset-1
+    column ``c1``."""
+    if getattr(prog, 'layout', None) not in ('coo', 'csr'):
+        raise ValueError("the normal matrix takes jacobian_layout='coo' or "
+                         "'csr'.")
+    side = [column_side(prog.n, prog.q, prog.method, k)
+            for _, k in prog.pattern]
+    sides = sorted({s for s in side if s[0] >= 0})
+    where = {s: c for c, s in enumerate(sides)}
+    ent = [[-1]*len(sides) for _ in range(prog.M)]
+    for e, (j, _) in enumerate(prog.pattern):
+        if side[e][0] >= 0:
+            assert ent[j][where[side[e]]] < 0
+            ent[j][where[side[e]]] = e
+    coupled = [(where[(row, 0)], where[(row, 1)], row)
+               for row, off in sides if off == 0 and (row, 1) in where]
+    return sides, ent, coupled
+
+
+def normal_blocks(prog, N, jac_values, d=None, delta_c=0.0):
+    """``(A, B)`` of the block-tridiagonal normal matrix ``S = Jc[:, :T]
+    diag(1/d[:T]) Jc[:, :T]^T + delta_c I`` (``Jc``: the ``M(N-1)``
+    collocation rows of the Jacobian, ``T = (n+q)N``) ordered by constraint
+    node: ``A`` of shape ``(N-1, M, M)``, the diagonal blocks, ``B`` of shape
+    ``(N-2, M, M)``, ``B[i] = S[i+1, i]``.  ``jac_values``: the values of
+    ``jacobian(free)`` in ``prog``'s layout (``'coo'``: ``jac[i*P + e]``,
+    ``'csr'``: ``jac[S_j*(N-1) + i*L_j + pos]``), pruned or not; ``d``:
+    ``num_free`` (or ``T``) positive values, default ones.  The host
+    statement of ``opty_normal_blocks``: with ``G_i`` the block of node ``i``
+    (a pruned entry 0),
+
+    * ``A[i][a, b] = sum_k G_i[a, k] (G_i[b, k] / d[row_k*N + i + off_k])``
+      over the trajectory columns in ascending ``(row, off)`` from ``+0.0``,
+      for ``a >= b``, mirrored; ``delta_c`` is added to a diagonal last;
+    * ``B[i][a, b] = sum_row G_{i+1}[a, k0(row)] (G_i[b, k1(row)] /
+      d[row*N + i + 1])`` over the free rows that have an offset-0 column
+      ``k0`` and an offset-1 column ``k1``, ascending.
+
+    The tail columns and the instance rows are not part of ``S`` (the kernel
+    fuses each product with its addition; this statement rounds both)."""
+    import numpy as np
+    N = int(N)
+    ncn = N - 1
+    if ncn < 1:
+        raise ValueError('N %d < 2' % N)
+    delta_c = float(delta_c)
+    if not (0.0 <= delta_c < np.inf):
+        raise ValueError('delta_c must be a finite value >= 0.')
+    sides, ent, coupled = normal_columns(prog)
+    M, P = prog.M, len(prog.pattern)
+    T = (prog.n + prog.q)*N
+    jac_values = np.asarray(jac_values, dtype=float).reshape(-1)
+    if len(jac_values) < P*ncn:
+        raise ValueError('jac_values must hold %d block values' % (P*ncn))
+    d = np.ones(T) if d is None else np.asarray(d, dtype=float).reshape(-1)
+    if len(d) < T:
+        raise ValueError('d must have at least %d values' % T)
+    i = np.arange(ncn, dtype=np.int64)
+    rs = prog.row_start
+
+    def entry(e):
+        if prog.layout == 'csr':
+            j = prog.pattern[e][0]
+            S, L = rs[j], rs[j + 1] - rs[j]
+            return jac_values[S*ncn + i*L + (e - S)]
+        return jac_values[i*P + e]
+    G = np.zeros((ncn, M, len(sides)))
+    for j in range(M):
+        for c, e in enumerate(ent[j]):
+            if e >= 0:
+                G[:, j, c] = entry(e)
+    A = np.zeros((ncn, M, M))
+    for c, (row, off) in enumerate(sides):
+        w = G[:, :, c]/d[row*N + i + off][:, None]
+        A = A + G[:, :, c][:, :, None]*w[:, None, :]
+    low = np.tril(A)
+    A = low + np.transpose(np.tril(A, -1), (0, 2, 1))
+    k = np.arange(M)
+    A[:, k, k] = A[:, k, k] + delta_c
+    B = np.zeros((max(ncn - 1, 0), M, M))
+    for c0, c1, row in coupled:
+        w = G[:-1, :, c1]/d[row*N + i[:-1] + 1][:, None]
+        B = B + G[1:, :, c0][:, :, None]*w[:, None, :]
+    return A, B
+
+
+def _normal_cholesky(A, level, rows):
+    """Batched lower Cholesky factors of the blocks ``A`` (rows ``rows`` of
+    level ``level``); a pivot that is not positive and finite raises
+    ``LinAlgError`` naming the level and the first such row."""
+    import numpy as np
+    try:
+        L = np.linalg.cholesky(A)
+        bad = ~np.all(np.isfinite(L), axis=(1, 2))
+    except np.linalg.LinAlgError:
+        L = np.zeros_like(A)
+        bad = np.zeros(len(A), dtype=bool)
+        for k in range(len(A)):
+            try:
+                L[k] = np.linalg.cholesky(A[k])
+            except np.linalg.LinAlgError:
+                bad[k] = True
+    if bad.any():
+        raise np.linalg.LinAlgError(
+            'the normal matrix is not positive definite: a pivot that is '
+            'not positive and finite at level %d, row %d'
+            % (level, rows[int(np.flatnonzero(bad)[0])]))
+    return L
+
+
+def _bt(X):
+    """The blocks of ``X`` transposed."""
+    import numpy as np
+    return np.transpose(X, (0, 2, 1))
+
+
+def normal_factor(A, B):
+    """Block cyclic reduction with Cholesky factors of the block-tridiagonal
+    matrix with diagonal blocks ``A`` ``(n, M, M)`` and couplings ``B``
+    ``(n-1, M, M)``, ``B[k] = S[k+1, k]`` -- a sparse Cholesky under an
+    odd-even ordering, no pivoting; the elimination order the kernels share.
+    Level ``l`` has ``n_l`` rows, ``n_0 = n``, ``n_{l+1} = ceil(n_l/2)``;
+    rows 1, 3, 5, ... are eliminated, rows 0, 2, 4, ... survive as ``e =
+    k/2``; a level with one row is a plain Cholesky.  Eliminated row ``k``:
+    ``L_k = chol(A_k)``, ``U_k = L_k^-1 S[k, k-1]``, ``V_k = L_k^-1 S[k,
+    k+1]`` (absent for a last row); survivors: ``A'_e = A_2e - U_{2e+1}^T
+    U_{2e+1} - V_{2e-1}^T V_{2e-1}``, ``S'[e+1, e] = -V_{2e+1}^T U_{2e+1}``.
+    Returns the list of levels ``(n_l, L, U, V)`` (``V`` zero where absent).
+    Only the lower triangle of a diagonal block is read.  Raises
+    ``numpy.linalg.LinAlgError`` naming level and row of the first pivot that
+    is not positive and finite."""
+    import numpy as np
+    A = np.array(A, dtype=float)
+    B = np.array(B, dtype=float)
+    n, M = A.shape[0], A.shape[1]
+    if A.shape != (n, M, M) or n < 1 or B.shape != (n - 1, M, M):
+        raise ValueError('A must have shape (n, M, M) and B (n - 1, M, M)')
+    levels = []
+    level = 0
+    while True:
+        n = len(A)
+        if n == 1:
+            levels.append((1, _normal_cholesky(A, level, [0]), None, None))
+            return levels
+        odd = np.arange(1, n, 2)
+        L = _normal_cholesky(A[odd], level, odd)
+        U = np.linalg.solve(L, B[odd - 1])
+        V = np.zeros_like(U)
+        inner = odd + 1 < n
+        V[inner] = np.linalg.solve(L[inner], _bt(B[odd[inner]]))
+        levels.append((n, L, U, V))
+        ne = (n + 1)//2
+        An = A[0::2].copy()
+        # survivor e < n//2 has the row 2e + 1 behind it, survivor e > 0 the
+        # row 2e - 1 in front (whose V exists)
+        An[:n//2] = An[:n//2] - _bt(U) @ U
+        An[1:] = An[1:] - _bt(V[:ne - 1]) @ V[:ne - 1]
+        A, B = An, -(_bt(V[:ne - 1]) @ U[:ne - 1])
+        level += 1
+
+
+def normal_solve(factors, r):
+    """``y = S^-1 r`` from ``factors`` of :func:`normal_factor`; ``r`` of
+    shape ``(M n,)`` or ``(M n, k)`` in the order of ``constraints(free)``,
+    ``j*n + i``.  Forward: ``z_k = L_k^-1 r_k``, ``r'_e = r_2e - U_{2e+1}^T
+    z_{2e+1} - V_{2e-1}^T z_{2e-1}``; backward: ``y_k = L_k^-T (z_k - U_k
+    y_{k-1} - V_k y_{k+1})``."""
+    import numpy as np
+    n0 = factors[0][0]
+    M = factors[0][1].shape[1]
+    r = np.asarray(r, dtype=float)
+    if r.ndim not in (1, 2) or r.shape[0] != M*n0:
+        raise ValueError('r must have shape (%d,) or (%d, k)' % (M*n0, M*n0))
+    rhs = r.reshape(M, n0, -1).transpose(1, 0, 2)       # (node, j, column)
+    zs = []
+    for n, L, U, V in factors:
+        if n == 1:
+            zs.append(np.linalg.solve(L, rhs))
+            break
+        z = np.linalg.solve(L, rhs[1::2])
+        zs.append(z)
+        ne = (n + 1)//2
+        nxt = rhs[0::2].copy()
+        nxt[:n//2] = nxt[:n//2] - _bt(U) @ z
+        nxt[1:] = nxt[1:] - _bt(V[:ne - 1]) @ z[:ne - 1]
+        rhs = nxt
+    y = np.linalg.solve(_bt(factors[-1][1]), zs[-1])
+    for (n, L, U, V), z in zip(factors[-2::-1], zs[-2::-1]):
+        full = np.empty((n,) + y.shape[1:])
+        full[0::2] = y
+        w = z - U @ y[:n//2]
+        inner = np.arange(1, n, 2) + 1 < n
+        w[inner] = w[inner] - V[inner] @ y[1:][:inner.sum()]
+        full[1::2] = np.linalg.solve(_bt(L), w)
+        y = full
+    return y.transpose(1, 0, 2).reshape(r.shape)
+
+
 def matrix_program(dag, outputs, num_vec, num_const, shape):
     """Program of a plain matrix of expressions (the reference's
     ``ufuncify_matrix`` call shape, ``opty/utils.py:639-640``): ``outputs`` are

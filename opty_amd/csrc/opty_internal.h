@@ -20,6 +20,9 @@
 //                     diagonal and CSR Jacobian as one CSR lower triangle;
 //                     borrows too, owns a CSR-Hessian handle, kernels of
 //                     its own)
+//   normal.cpp        the normal-matrix handle (the block-tridiagonal J D^-1
+//                     J^T formed, factorised by block cyclic reduction and
+//                     solved with; borrows too, kernels of its own)
 //   referee.cpp       (libopty_hip_referee.so) instruction-tape kernel and
 //                     register poisoner of the build verification
 #pragma once

@@ -1828,6 +1828,63 @@ class ConstraintCollocator(object):
         evaluate.__doc__ = 'data of kkt_csr_structure() at (free, lagrange).'
         return evaluate
 
+    # ------------------------------------------------------------------
+    # Normal matrix: a direct solve with the block-tridiagonal J D^-1 J^T
+    # 
+    # ------------------------------------------------------------------
+    def generate_normal_solver(self):
+        """Returns ``ns``, a :class:`opty_amd.normal.NormalSolver`: the
+        direct solver with the constraint normal matrix ``S = Jc[:, :T]
+        diag(1/d[:T]) Jc[:, :T]^T + delta_c I`` -- ``Jc`` the ``M(N-1)``
+        collocation rows of the Jacobian, ``T = (n+q)N`` the trajectory part
+        of ``free`` --, which is symmetric block tridiagonal when ordered by
+        constraint node.  ``ns.factor(free, d=None, delta_c=0.0)`` evaluates
+        the Jacobian into a device buffer of its own, forms ``S`` and
+        factorises it on the GPU (block cyclic reduction with Cholesky
+        factors); ``ns.factor_values(jac_values, ...)`` does the same for
+        values the caller holds; ``ns.solve(r)`` applies ``S^-1`` to ``r`` of
+        shape ``(M(N-1),)`` or ``(M(N-1), k)``; ``ns.blocks(jac_values,
+        d=None, delta_c=0.0)`` returns ``(A, B)``, the blocks themselves;
+        ``ns.workspace_bytes`` is the device memory of the factors.  A pivot
+        that is not positive and finite raises ``numpy.linalg.LinAlgError``.
+
+        The tail columns (unknown parameters, a free interval) and the
+        instance rows are not part of ``S``: it is all of ``J D^-1 J^T``
+        only for a problem that has neither, otherwise a preconditioner.
+        Takes ``jacobian_layout`` ``'coo'`` and ``'csr'``, pruned or not;
+        one solver per collocator."""
+        if self._jacobian_layout not in ('coo', 'csr'):
+            # (refused before a device is asked for)
+            raise ValueError(
+                "generate_normal_solver needs jacobian_layout='coo' or "
+                "'csr', not %r." % self._jacobian_layout)
+        if getattr(self, '_normal_solver', None) is None:
+            prog = self._build_program()
+
+            def create(hip):
+                return hb.HipNormalSolver(hip, dict(
+                    M=prog.M, layout=self._jacobian_layout,
+                    pattern=prog.pattern)), {}
+            # (no program of its own: the handle is held to the host
+            # statement and to scipy.sparse by the test suite)
+            handle = self._ensure_derived('_normal', create,
+                                          lambda handle: None)
+            from .normal import NormalSolver
+            self._normal_solver = NormalSolver(self, handle)
+        return self._normal_solver
+
+    def normal_operator(self, free, d=None, delta_c=0.0):
+        """``S^-1`` of :meth:`generate_normal_solver` at ``free`` as a
+        symmetric ``scipy.sparse.linalg.LinearOperator`` of shape ``(M(N-1),
+        M(N-1))``: ``S`` is factorised once, here, and every ``matvec`` /
+        ``matmat`` is one ``ns.solve``.  The factors live in the collocator's
+        solver: a product after a later factorisation raises
+        ``RuntimeError``.  A torch CUDA vector is answered with a CUDA
+        tensor."""
+        solver = self.generate_normal_solver()
+        solver.factor(free, d, delta_c)
+        return solver.operator()
+
     def generate_source(self):
         """HIP source of this problem's kernels and its launch metadata."""
         return self._emit(self._printer_options())
@@ -3808,6 +3865,12 @@ class Problem(object):
         (:meth:`ConstraintCollocator.jacobian_operator`)."""
         return self.collocator.jacobian_operator(free)
 
+    def normal_operator(self, free, d=None, delta_c=0.0):
+        """The inverse of the constraint normal matrix at ``free`` as a
+        ``scipy.sparse.linalg.LinearOperator``
+        (:meth:`ConstraintCollocator.normal_operator`)."""
+        return self.collocator.normal_operator(free, d, delta_c)
+
     def intermediate(self, *args):
         self.obj_value.append(args[2])
 
@@ -3963,7 +4026,7 @@ class ShardedProblem(Problem):
     ``num_free`` doubles each way per product; :meth:`hessian_operator`
     itself keeps refusing.  Not sharded: the objective's Hessian (the root
     alone evaluates and multiplies it), block products, ``hessian_csr`` /
-    ``kkt_csr``; the torch-free host (``shard_host.py``) and the C client
+    ``kkt_csr``, ``normal_operator``; the torch-free host (``shard_host.py``) and the C client
     do not serve the Hessian.
 
     Extra keywords: ``group`` (process group), ``root`` (solver rank),
@@ -4013,6 +4076,11 @@ class ShardedProblem(Problem):
                 delta_w=0.0, delta_c=0.0):
         raise NotImplementedError('the Hessian is not sharded: '
                                   'ShardedProblem has no kkt_csr.')
+
+    def normal_operator(self, free, d=None, delta_c=0.0):
+        raise NotImplementedError(
+            'the normal-matrix solver is not sharded: ShardedProblem has '
+            'no normal_operator.')
 
     def _install_hessian(self, obj_hessian):
         """``hessianstructure()`` and ``hessian(free, lagrange,

@@ -76,7 +76,7 @@ def _hipcc():
 #: where) and of the build referee's own library
 RUNTIME_SOURCES = ('runtime.cpp', 'programs.cpp', 'host_scatter.cpp',
                    'comm.cpp', 'hessian.cpp', 'jacprod.cpp', 'hessmv.cpp',
-                   'hesscsr.cpp', 'kktcsr.cpp')
+                   'hesscsr.cpp', 'kktcsr.cpp', 'normal.cpp')
 REFEREE_SOURCES = ('referee.cpp',)
 REFEREE_PATH = os.path.join(_PKG, 'libopty_hip_referee.so')
 
@@ -417,6 +417,11 @@ class _HessmvDesc(ctypes.Structure):
             'tail_cols')]
 
 
+class _NormalDesc(ctypes.Structure):
+    _fields_ = [('M', ctypes.c_int32), ('P', ctypes.c_int32),
+                ('layout', ctypes.c_int32), ('pattern', ctypes.c_void_p)]
+
+
 class _JacprodDesc(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in (
         'jvp_strips', 'vjp_strips', 'num_tail', 'nnz_inst')]
@@ -631,6 +636,21 @@ _SIGNATURES = {
     'opty_hip_kktcsr_assemble_timed': (ctypes.c_int,
                                        [_P, _P, _P, _P, ctypes.c_double,
                                         ctypes.c_double, _P, _P]),
+    'opty_hip_normal_create': (ctypes.c_int,
+                               [_P, ctypes.POINTER(_NormalDesc),
+                                ctypes.POINTER(_P)]),
+    'opty_hip_normal_destroy': (ctypes.c_int, [_P]),
+    'opty_hip_normal_workspace_bytes': (ctypes.c_int64, [_P]),
+    'opty_hip_normal_max_equations': (ctypes.c_int32, [_P]),
+    'opty_hip_normal_blocks': (ctypes.c_int,
+                               [_P, _P, _P, ctypes.c_double, _P, _P,
+                                ctypes.c_int32]),
+    'opty_hip_normal_factor': (ctypes.c_int,
+                               [_P, _P, _P, ctypes.c_double, ctypes.c_int32]),
+    'opty_hip_normal_factor_status': (ctypes.c_int, [_P, _P, _P]),
+    'opty_hip_normal_solve': (ctypes.c_int,
+                              [_P, _P, _P, ctypes.c_int32, ctypes.c_int64,
+                               ctypes.c_int32]),
     'opty_hip_output_register': (ctypes.c_int, [_P, _P, ctypes.c_int64,
                                                 ctypes.c_int64]),
     'opty_hip_output_unregister': (ctypes.c_int, [_P, _P]),
@@ -1693,3 +1713,69 @@ class HipKktCsr(_HessianTripletsHandle):
             None if sigma is None else _ptr(sigma), float(delta_w),
             float(delta_c), _ptr(data), _ptr(ms)))
         return tuple(float(x) for x in ms)
+
+
+class HipNormalSolver(_DerivedHandle):
+    """One ``opty_hip_normal`` handle: the block-tridiagonal normal matrix
+    ``S = Jc[:, :T] diag(1/d[:T]) Jc[:, :T]^T + delta_c I`` of a
+    :class:`HipProblem`, formed from the Jacobian's values, factorised by
+    block cyclic reduction with Cholesky factors and solved with, all on the
+    device (``include/opty_hip.h``, "Normal matrix").  ``desc`` holds ``M``,
+    ``layout`` (``'coo'`` / ``'csr'``) and ``pattern``, the ``(j, k)`` of the
+    stored block entries.  It borrows its problem for sizes, method, device
+    and stream (no code object: the kernels are the runtime library's) and
+    is released and created again with the problem's C handle, as the other
+    derived handles are."""
+
+    _create, _destroy = 'opty_hip_normal_create', 'opty_hip_normal_destroy'
+    _LAYOUTS = {'coo': 0, 'csr': 1}
+
+    def __init__(self, problem, desc):
+        self._pattern = np.ascontiguousarray(
+            desc['pattern'], dtype=np.int32).reshape(-1, 2)
+        self.M = int(desc['M'])
+        # (an explicit count: what the error-path tests hand over on purpose)
+        self.P = int(desc.get('P', len(self._pattern)))
+        layout = desc.get('layout', 'coo')
+        self._layout = self._LAYOUTS.get(layout, layout)
+        super().__init__(problem, None)
+
+    def _descriptor(self):
+        return _NormalDesc(
+            M=self.M, P=self.P, layout=int(self._layout),
+            pattern=_ptr(self._pattern) if self._pattern.size else None)
+
+    @property
+    def workspace_bytes(self):
+        """Device memory the handle owns for the levels and its tables."""
+        return int(self._lib.opty_hip_normal_workspace_bytes(self._handle()))
+
+    @property
+    def max_equations(self):
+        """The largest ``M`` a handle on this device takes."""
+        return int(self._lib.opty_hip_normal_max_equations(self._handle()))
+
+    def blocks(self, jac_values, d, delta_c, A, B, mem):
+        _check(self._lib.opty_hip_normal_blocks(
+            self._handle(), _ptr(jac_values), None if d is None else _ptr(d),
+            float(delta_c), _ptr(A), _ptr(B), mem))
+
+    def factor(self, jac_values, d, delta_c, mem):
+        """Enqueues (``DEVICE``) or runs (``HOST``) the factorisation;
+        :meth:`status` says how it went."""
+        _check(self._lib.opty_hip_normal_factor(
+            self._handle(), _ptr(jac_values), None if d is None else _ptr(d),
+            float(delta_c), mem))
+
+    def status(self):
+        """``None`` after a factorisation whose pivots were all positive and
+        finite, else ``(level, row)`` of the first one that was not; waits
+        for the factorisation."""
+        level, row = ctypes.c_int32(), ctypes.c_int64()
+        _check(self._lib.opty_hip_normal_factor_status(
+            self._handle(), ctypes.addressof(level), ctypes.addressof(row)))
+        return None if level.value < 0 else (level.value, row.value)
+
+    def solve(self, r, y, ncols, ld, mem):
+        _check(self._lib.opty_hip_normal_solve(
+            self._handle(), _ptr(r), _ptr(y), int(ncols), int(ld), mem))
